@@ -13,8 +13,10 @@ independent Brain engine — the DP-replica deployment of SURVEY.md §2.5 — on
 streams keeps exactly one chain in flight and submits its next chain the moment its verdict returns, so a step is
 ``--streams`` completed chains with no wave boundary (no straggler tail; new prompts are prefilled in the same forward
 as the live decode rows — mixed steps — and the prefix cache stays warm as in a long-running server).  The headline
-stays the wave form above; after it, ``--closed-steps`` closed-loop steps are timed too and reported as
-``closed_loop_chains_s`` / ``closed_loop_p50_ms`` / ``closed_loop_p99_ms`` in the same JSON line.
+stays the wave form above; with ``--full``, ``--closed-steps`` closed-loop steps are timed after it and reported as
+``closed_loop_chains_s`` / ``closed_loop_p50_ms`` / ``closed_loop_p99_ms`` in the same JSON line, and so is the
+single-stream latency (``--single-stream`` chains, one in flight at a time: ``single_stream_*``).  A plain run sets
+up, warms up, times ``--steps`` steps, writes ``--dump-outputs DIR`` if asked and prints the result line.
 
 Weights are random-init Llama-3-8B (real architecture, bf16, no checkpoint offline); data is synthetic telemetry.
 Work per GPU is fixed as N grows (weak scaling).  Rank 0 prints ONE JSON line.
@@ -73,8 +75,8 @@ def parse():
                     help="separate prefill steps (no prefill chunks riding in the decode batch's forward)")
     ap.add_argument("--mode", choices=["wave", "closed"], default="wave")
     ap.add_argument("--closed-steps", type=int, default=6,
-                    help="wave mode: afterwards also time this many closed-loop steps (steady-state arrivals) and "
-                         "report them as closed_loop_* next to the headline (0 = skip)")
+                    help="wave mode with --full: afterwards also time this many closed-loop steps (steady-state "
+                         "arrivals) and report them as closed_loop_* next to the headline (0 = skip)")
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8 = W8A8 e4m3 projections on the block-scaled MFMA / hipBLASLt fp8 (not the headline)")
     ap.add_argument("--device", default="cuda")
@@ -84,7 +86,31 @@ def parse():
     ap.add_argument("--max-model-len", type=int, default=512)
     ap.add_argument("--sequence-parallel", action="store_true",
                     help="with --tp: Megatron sequence parallelism in prefill (reduce-scatter / all-gather)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the secondary measurements: the closed-loop steps "
+                         "(--closed-steps, closed_loop_* in the result) and the single-stream latency phase "
+                         "(--single-stream, single_stream_* in the result).  Off: only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32): out_ids [chains, num_predict] (token ids of each verdict in "
+                         "submission order, padded with -1), out_len [chains], prompt_len [chains]")
     return ap.parse_args()
+
+
+def dump_outputs(path, last, num_predict):
+    """The last timed step's results as float32 arrays (token ids are < 2**24, exact in float32).  ``last`` is that
+    step's requests in submission order; inputs and weights are seeded, so two builds run with the same arguments
+    can be compared array for array."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    width = max([num_predict] + [len(r.out_ids) for r in last])
+    ids = np.full((len(last), width), -1.0, dtype=np.float32)
+    for i, r in enumerate(last):
+        ids[i, :len(r.out_ids)] = r.out_ids
+    np.save(os.path.join(path, "out_ids.npy"), ids)
+    np.save(os.path.join(path, "out_len.npy"), np.asarray([len(r.out_ids) for r in last], dtype=np.float32))
+    np.save(os.path.join(path, "prompt_len.npy"), np.asarray([len(r.prompt_ids) for r in last], dtype=np.float32))
 
 
 def run_closed(a, eng, prompts, barrier, progress, steps=None, warmup=None, step_times=None):
@@ -219,8 +245,10 @@ def main():
     total_steps = a.warmup + a.steps
     per_stream = total_steps if a.mode == "wave" else 2 * total_steps + 2  # closed loop: fast streams cycle more
     closed_warm = 2  # closed-loop warmup steps (the prefix cache and decode buckets settle)
-    closed_per = 2 * (closed_warm + a.closed_steps) + 2 if a.mode == "wave" and a.closed_steps > 0 else 0
-    chains = synthetic_chains(a.streams * (per_stream + closed_per) + a.single_stream, seed=1000 + replica)
+    # the closed-loop steps after the wave headline and the single-stream phase run only with --full
+    closed_per = 2 * (closed_warm + a.closed_steps) + 2 if a.full and a.mode == "wave" and a.closed_steps > 0 else 0
+    n_single = a.single_stream if a.full else 0
+    chains = synthetic_chains(a.streams * (per_stream + closed_per) + n_single, seed=1000 + replica)
     prompts = [build_prompt(c.history) for c in chains]
     n_main, n_closed = a.streams * per_stream, a.streams * closed_per
 
@@ -278,6 +306,8 @@ def main():
     hist = collections.Counter(min(len(r.out_ids) // 4 * 4, 64) for r in timed)
     progress("verdict length histogram (4-token bins): " + json.dumps(dict(sorted(hist.items()))))
     prompt_tok = sum(len(r.prompt_ids) for r in timed)
+    if a.dump_outputs and rank == 0:  # rank 0's replica; submission order (rid) also in closed mode
+        dump_outputs(a.dump_outputs, sorted(timed[-a.streams:], key=lambda r: r.rid), a.num_predict)
 
     closed = None
     if closed_per:  # steady-state arrivals after the wave headline
@@ -342,12 +372,15 @@ def main():
             },
             "p50_verdict_latency_ms": round(1000 * statistics.median(lats), 2),
             "p99_verdict_latency_ms": round(1000 * sorted(lats)[max(0, math.ceil(0.99 * len(lats)) - 1)], 2),
-            "single_stream_p50_latency_ms": round(1000 * statistics.median(singles), 2) if singles else None,
-            "single_stream_decode_ms_per_token": round(
-                1000 * sum(t for s in allst for t, _ in s["single_tok"])
-                / max(1, sum(n for s in allst for _, n in s["single_tok"])), 3),
-            "single_stream_verdict_tokens": round(
-                sum(n for s in allst for _, n in s["single_tok"]) / max(1, sum(len(s["single_tok"]) for s in allst)), 1),
+            **({
+                "single_stream_p50_latency_ms": round(1000 * statistics.median(singles), 2) if singles else None,
+                "single_stream_decode_ms_per_token": round(
+                    1000 * sum(t for s in allst for t, _ in s["single_tok"])
+                    / max(1, sum(n for s in allst for _, n in s["single_tok"])), 3),
+                "single_stream_verdict_tokens": round(
+                    sum(n for s in allst for _, n in s["single_tok"])
+                    / max(1, sum(len(s["single_tok"]) for s in allst)), 1),
+            } if a.full else {}),  # the single-stream phase runs only with --full
             "verdicts_valid": f"{oks}/{n}",
             "prompt_tokens_per_chain": round(sum(s["ptok"] for s in allst) / n, 1),
             "verdict_tokens_per_chain": round(sum(s["gen"] for s in allst) / n, 1),

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 O=gpurun_out/${R6OUT:-r6bench}
 mkdir -p $O
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | tail -1 > $O/bench.json
 cut -c1-1200 $O/bench.json
 bash scripts/trace_keep.sh > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 1; }

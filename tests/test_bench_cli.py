@@ -68,6 +68,35 @@ def test_bench_gpus_flag_self_launches():
     assert r["n_gpus"] == 2 and r["config"]["parallelism"] == "dp2" and r["verdicts_valid"] == "6/6"
 
 
+@pytest.mark.slow
+def test_bench_plain_vs_full_and_dump_outputs(tmp_path):
+    """A plain run measures the headline only; --full adds the closed-loop and single-stream figures to the same
+    line.  --dump-outputs writes the last timed step's verdict tokens as float32 .npy, identical between the two runs
+    (same arguments -> same inputs and weights), and --steps sets the number of timed steps."""
+    import numpy as np
+
+    res = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--closed-steps", "1"])):
+        out = _run_plain(["--gpus", "1", "--dump-outputs", str(tmp_path / name)] + extra)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        res[name] = json.loads(lines[0])
+    for r in res.values():
+        assert r["steps"] == 1 and r["verdicts_valid"] == "3/3" and r["ms_per_step"] > 0 and r["unit"] == "chains/s"
+        assert abs(r["value"] * r["ms_per_step"] / 1000 - 3) < 0.01  # value = chains of the timed steps / their time
+    assert not [k for k in res["plain"] if k.startswith(("closed_loop_", "single_stream_"))]
+    assert res["full"]["closed_loop_chains_s"] > 0 and res["full"]["single_stream_p50_latency_ms"] > 0
+    assert set(res["full"]) - set(res["plain"]) == {k for k in res["full"]
+                                                     if k.startswith(("closed_loop_", "single_stream_"))}
+    for n in ("out_ids", "out_len", "prompt_len"):
+        a, b = np.load(tmp_path / "plain" / f"{n}.npy"), np.load(tmp_path / "full" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.shape[0] == 3 and np.array_equal(a, b), n
+    ids, ln = np.load(tmp_path / "plain" / "out_ids.npy"), np.load(tmp_path / "plain" / "out_len.npy")
+    assert ids.shape[1] >= 24 and (ln > 0).all()
+    assert all((ids[i, :int(k)] >= 0).all() and (ids[i, int(k):] == -1).all() for i, k in enumerate(ln))
+
+
 def test_bench_gpus_mismatch_is_an_error():
     out = _run_plain(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"}, timeout=300)
     assert out.returncode != 0 and "disagrees with WORLD_SIZE" in out.stderr
