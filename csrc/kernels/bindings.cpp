@@ -38,6 +38,12 @@ void launch_paged_attn(const uint16_t*, const void*, const void*, const int32_t*
 void launch_constrained_sample(const void*, bool, int64_t, const int32_t*, int, int, const int16_t*, const int16_t*,
                                const int16_t*, int, int32_t*, int32_t*, const float*, const int32_t*, const int32_t*, const float*,
                                int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int, hipStream_t);
+void launch_token_logprobs(const void*, bool, int64_t, const int32_t*, int, int, const int16_t*, const int16_t*, int,
+                           const int32_t*, const int32_t*, const int32_t*, const int32_t*, int32_t*, float*, int32_t*,
+                           float*, int, hipStream_t);
+void launch_token_logprobs_commit(const void*, bool, int64_t, int, const int32_t*, int, const int32_t*,
+                                  const int32_t*, int, const int32_t*, const int32_t*, const float*, const int32_t*,
+                                  const float*, int, float*, int32_t*, hipStream_t);
 void launch_gemv(const uint16_t*, int, int, const uint16_t*, int, uint16_t*, bool, hipStream_t);
 void attn_init();
 void launch_gemm(const uint16_t*, const uint16_t*, uint16_t*, int, int, int, bool, int, hipStream_t);
@@ -384,6 +390,87 @@ void constrained_sample(const Tensor& logits, const c10::optional<Tensor>& row_o
                                        (int)done_state, i32m(state), i32m(remaining), tp, sp, kp, pp, i32m(ids),
                                        i32m(pos), i32m(ctx), i32m(nout), i32m(out_tokens), (int)out_tokens.size(1),
                                        cur_stream());
+}
+
+// Per-token logprobs (csrc/kernels/logprobs.hip).  Shared checks of the per-slot scratch: lp_want / lp_mark / lp_lse
+// one entry per slot, lp_top_ids / lp_top_val [slots, K] with K <= 20.  Returns K.
+int64_t chk_lp_scratch(int64_t n, const Tensor& lp_want, const Tensor& lp_mark, const Tensor& lp_lse,
+                       const Tensor& lp_top_ids, const Tensor& lp_top_val) {
+    chk_i32(lp_want, "lp_want");
+    chk_i32(lp_mark, "lp_mark");
+    chk_gpu(lp_lse, "lp_lse");
+    chk_i32(lp_top_ids, "lp_top_ids");
+    chk_gpu(lp_top_val, "lp_top_val");
+    CHK(lp_lse.scalar_type() == at::kFloat && lp_top_val.scalar_type() == at::kFloat, "lp_lse / lp_top_val f32");
+    CHK(lp_want.numel() >= n && lp_mark.numel() >= n && lp_lse.numel() >= n, "lp_*: one entry per slot");
+    CHK(lp_top_ids.dim() == 2 && lp_top_val.dim() == 2 && lp_top_ids.size(0) >= n && lp_top_val.size(0) >= n &&
+            lp_top_ids.size(1) == lp_top_val.size(1),
+        "lp_top_ids / lp_top_val [slots, K]");
+    CHK(lp_top_ids.size(1) <= 20, "at most 20 top logprobs (MAX_TOP)");
+    return lp_top_ids.size(1);
+}
+
+const int32_t* chk_lp_rows(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, int64_t n) {
+    CHK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits [rows, V] row-contiguous");
+    CHK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16 or f32");
+    if (row_of_slot.has_value()) {
+        chk_i32(*row_of_slot, "row_of_slot");
+        CHK(row_of_slot->numel() >= n, "row_of_slot: one entry per slot");
+        return i32(*row_of_slot);
+    }
+    CHK(logits.size(0) >= n, "one logits row per slot");
+    return nullptr;
+}
+
+void token_logprobs(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, const Tensor& next,
+                    const Tensor& dist, int64_t done_state, const Tensor& state, const Tensor& remaining,
+                    const Tensor& nout, const Tensor& lp_want, const Tensor& lp_mark, const Tensor& lp_lse,
+                    const Tensor& lp_top_ids, const Tensor& lp_top_val) {
+    chk_gpu(next, "next");
+    CHK(next.scalar_type() == at::kShort && next.dim() == 2, "next must be int16 [S, V]");
+    chk_gpu(dist, "dist");
+    CHK(dist.scalar_type() == at::kShort && dist.numel() == next.size(0), "dist must be int16 [S]");
+    const int64_t vocab = next.size(1);
+    chk_i32(state, "state");
+    const int64_t n = state.numel();
+    const int32_t* rp = chk_lp_rows(logits, row_of_slot, n);
+    CHK(logits.size(1) >= vocab, "logits narrower than the DFA vocabulary");
+    chk_i32(remaining, "remaining");
+    chk_i32(nout, "nout");
+    CHK(remaining.numel() >= n && nout.numel() >= n, "slot tensors must have one entry per slot");
+    const int64_t K = chk_lp_scratch(n, lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+    chronos::launch_token_logprobs(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0), rp, (int)n,
+                                   (int)vocab, next.data_ptr<int16_t>(), dist.data_ptr<int16_t>(), (int)done_state,
+                                   i32(state), i32(remaining), i32(nout), i32(lp_want), i32m(lp_mark),
+                                   lp_lse.data_ptr<float>(), i32m(lp_top_ids), lp_top_val.data_ptr<float>(), (int)K,
+                                   cur_stream());
+}
+
+void token_logprobs_commit(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, const Tensor& nout,
+                           const Tensor& out_tokens, const Tensor& lp_want, const Tensor& lp_mark,
+                           const Tensor& lp_lse, const Tensor& lp_top_ids, const Tensor& lp_top_val,
+                           const Tensor& out_lp, const Tensor& out_lp_ids) {
+    chk_i32(nout, "nout");
+    const int64_t n = nout.numel();
+    const int32_t* rp = chk_lp_rows(logits, row_of_slot, n);
+    const int64_t K = chk_lp_scratch(n, lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val);
+    chk_i32(out_tokens, "out_tokens");
+    CHK(out_tokens.dim() == 2 && out_tokens.size(0) >= n, "out_tokens [slots, max_out]");
+    const int64_t max_out = out_tokens.size(1);
+    chk_gpu(out_lp, "out_lp");
+    chk_i32(out_lp_ids, "out_lp_ids");
+    CHK(out_lp.scalar_type() == at::kFloat && out_lp.dim() == 3 && out_lp.size(0) >= n && out_lp.size(1) == max_out &&
+            out_lp.size(2) == 1 + K,
+        "out_lp f32 [slots, max_out, 1 + K]");
+    CHK(out_lp_ids.dim() == 3 && out_lp_ids.size(0) >= n && out_lp_ids.size(1) == max_out && out_lp_ids.size(2) == K,
+        "out_lp_ids int32 [slots, max_out, K]");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+    chronos::launch_token_logprobs_commit(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0),
+                                          (int)logits.size(1), rp, (int)n, i32(nout), i32(out_tokens), (int)max_out,
+                                          i32(lp_want), i32(lp_mark), lp_lse.data_ptr<float>(), i32(lp_top_ids),
+                                          lp_top_val.data_ptr<float>(), (int)K, out_lp.data_ptr<float>(),
+                                          i32m(out_lp_ids), cur_stream());
 }
 
 // y = x @ w.T for M <= 8 rows (decode); swiglu: w = [gate; up] -> y = silu(x@gate.T) * (x@up.T)
@@ -863,6 +950,12 @@ TORCH_LIBRARY(chronos, m) {
           "Tensor(a!) state, Tensor(b!) remaining, Tensor? temperature, Tensor? seed, Tensor(c!) ids, Tensor(d!) pos, "
           "Tensor(e!) ctx, Tensor(f!) nout, Tensor(g!) out_tokens, Tensor? topk=None, Tensor? topp=None, "
           "Tensor? jump=None) -> ()");
+    m.def("token_logprobs(Tensor logits, Tensor? row_of_slot, Tensor next, Tensor dist, int done_state, Tensor state, "
+          "Tensor remaining, Tensor nout, Tensor lp_want, Tensor(a!) lp_mark, Tensor(b!) lp_lse, Tensor(c!) lp_top_ids, "
+          "Tensor(d!) lp_top_val) -> ()");
+    m.def("token_logprobs_commit(Tensor logits, Tensor? row_of_slot, Tensor nout, Tensor out_tokens, Tensor lp_want, "
+          "Tensor lp_mark, Tensor lp_lse, Tensor lp_top_ids, Tensor lp_top_val, Tensor(a!) out_lp, "
+          "Tensor(b!) out_lp_ids) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
@@ -884,6 +977,8 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("paged_attention", &paged_attention);
     m.impl("decode_attention_rope", &decode_attention_rope);
     m.impl("constrained_sample", &constrained_sample);
+    m.impl("token_logprobs", &token_logprobs);
+    m.impl("token_logprobs_commit", &token_logprobs_commit);
     m.impl("ar_all_reduce", &ar_all_reduce);
     m.impl("ar_all_reduce_norm", &ar_all_reduce_norm);
 }

@@ -12,14 +12,40 @@ stream=true NDJSON, timing fields in ns) and /api/chat are served too so any Oll
 * ``keep_alive`` is accepted; the weights stay resident regardless (warm at start-up, quirk X8);
 * ``options.repeat_penalty`` / ``frequency_penalty`` / ``presence_penalty`` are accepted and not applied (the
   verdict sampler is grammar-constrained greedy; a penalty != 1 / 0 is reported in the reply's ``ignored_options``).
+
+Per-token logprobs (``"logprobs": true`` and optionally ``"top_logprobs": n``, 0 <= n <= 20, both top-level, for
+generate and chat).  The reply gains ``"logprobs": [{"token", "logprob", "bytes", "top_logprobs": [{"token",
+"logprob", "bytes"}, ...]}, ...]``, one entry per generated token (for chat beside ``message``).  Semantics, for the
+token sampled at output index i (csrc/kernels/logprobs.hip computes them on the device, inside the decode step):
+
+* the *legal set* is exactly the sampler's: tokens the request's grammar (``format``) allows in its current state and
+  that still let the output close within ``num_predict`` (budget forcing);
+* ``logprob(v) = logit[v] - logsumexp(logit[u] for legal u)``: raw logits, natural log, temperature 1, taken BEFORE
+  any top-k / top-p truncation — whatever the request's temperature, top_k or top_p.  A token the grammar forces (one
+  legal token) has logprob exactly 0.0; without a ``format`` this is the ordinary log-softmax (up to budget forcing
+  near ``num_predict``);
+* ``top_logprobs`` lists the n legal tokens with the largest logits, ordered by logit descending, then token id
+  ascending; shorter when fewer than n tokens are legal; alternatives whose logprob is -inf are dropped (JSON cannot
+  carry them; a chosen token's -inf would be ``null``);
+* ``token`` is the token's bytes decoded as UTF-8 (invalid sequences replaced), ``bytes`` the bytes themselves: the
+  ``bytes`` of all entries concatenate to the response's UTF-8;
+* with ``stop``, only the entries of tokens that lie wholly inside the returned text are kept;
+* deviation from Ollama: with ``stream: true`` the final (``done``) chunk carries the whole list instead of every chunk
+  carrying its own tokens', and a streamed reply that is cut at a stop string carries none;
+* while a request that wants logprobs is decoding, jump-forward over grammar-forced runs is suppressed for its batch
+  (EngineConfig.max_logprobs);
+* a backend that cannot produce them (server started with ``--max-logprobs 0``, the fake backend) answers normally and
+  names ``"logprobs"`` in ``ignored_options``.
 """
 from __future__ import annotations
 
+import math
 import time
 from dataclasses import dataclass
 from typing import Any, Optional
 
 OLLAMA_VERSION = "0.5.7-chronos"
+MAX_TOP_LOGPROBS = 20  # Ollama's cap on top_logprobs (and the kernels': chronos.ops.MAX_TOP_LOGPROBS)
 
 
 class BadRequest(ValueError):
@@ -45,6 +71,7 @@ class GenerateParams:
     context: Optional[list] = None
     keep_alive: Any = None
     ignored: tuple = ()
+    logprobs: int = -1  # -1 = not asked, 0 = the generated tokens' logprobs, n = with the top n alternatives
 
     @classmethod
     def parse(cls, body: dict, chat: bool = False, default_temperature: float = 0.0) -> "GenerateParams":
@@ -85,6 +112,16 @@ class GenerateParams:
                 raise BadRequest("context must be a list of token ids")
             p.context = ctx
         p.keep_alive = body.get("keep_alive")
+        lp, top = body.get("logprobs"), body.get("top_logprobs")
+        if lp is not None and not isinstance(lp, bool):
+            raise BadRequest("logprobs must be true or false")
+        if top is not None:
+            if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= MAX_TOP_LOGPROBS:
+                raise BadRequest(f"top_logprobs must be an integer from 0 to {MAX_TOP_LOGPROBS}")
+            if not lp:
+                raise BadRequest("top_logprobs requires logprobs: true")
+        if lp:
+            p.logprobs = int(top or 0)
         p.ignored = tuple(k for k, neutral in (("repeat_penalty", 1.0), ("frequency_penalty", 0.0),
                                                ("presence_penalty", 0.0))
                           if k in opts and float(opts[k]) != neutral)
@@ -150,10 +187,8 @@ def apply_stop(text: str, stop: tuple) -> tuple[str, bool]:
     return (text[:cut], True) if cut >= 0 else (text, False)
 
 
-def stop_context_ids(tok, prompt_ids, out_ids, visible: str) -> list:
-    """The continuation ``context`` of a reply cut at a stop string: the prompt, the generated tokens that lie wholly
-    inside the text the client received, then the re-tokenised remainder of that text — never the stop string or
-    what followed it (a continuation must not condition on text the client never saw)."""
+def _visible_tokens(tok, out_ids, visible: str) -> tuple[int, int]:
+    """(k, pos): the first k generated tokens lie wholly inside ``visible`` and cover its first ``pos`` bytes."""
     table = tok.token_bytes_list()
     vb = visible.encode("utf-8")
     pos, k = 0, 0
@@ -163,14 +198,51 @@ def stop_context_ids(tok, prompt_ids, out_ids, visible: str) -> list:
             break
         pos += len(b)
         k += 1
-    rest = vb[pos:].decode("utf-8", errors="ignore")
+    return k, pos
+
+
+def stop_context_ids(tok, prompt_ids, out_ids, visible: str) -> list:
+    """The continuation ``context`` of a reply cut at a stop string: the prompt, the generated tokens that lie wholly
+    inside the text the client received, then the re-tokenised remainder of that text — never the stop string or
+    what followed it (a continuation must not condition on text the client never saw)."""
+    k, pos = _visible_tokens(tok, out_ids, visible)
+    rest = visible.encode("utf-8")[pos:].decode("utf-8", errors="ignore")
     return [int(t) for t in list(prompt_ids) + list(out_ids[:k])] + ([int(t) for t in tok.encode(rest)] if rest else [])
 
 
-def chat_response(model: str, req) -> dict:
+def chat_response(model: str, req, ignored: tuple = ()) -> dict:
     d = {"model": model, "created_at": now_iso(), "message": {"role": "assistant", "content": req.text}}
     d.update(final_fields(req))
+    if ignored:
+        d["ignored_options"] = list(ignored)
     return d
+
+
+def logprobs_field(tok, req, visible: Optional[str] = None) -> Optional[list]:
+    """The reply's ``logprobs`` list from a finished request's ``out_logprobs`` (module docstring), or None when the
+    backend produced none (the caller then reports "logprobs" in ``ignored_options``).  ``visible``: the text
+    returned after a stop-string cut — only the tokens wholly inside it keep their entries."""
+    if tok is None or getattr(req, "logprobs", -1) < 0:
+        return None
+    ids, lps = list(req.out_ids), list(getattr(req, "out_logprobs", None) or [])
+    if len(lps) != len(ids):
+        return None
+    if visible is not None:
+        k, _ = _visible_tokens(tok, ids, visible)
+        ids, lps = ids[:k], lps[:k]
+    table = tok.token_bytes_list()
+
+    def entry(t: int, lp: float) -> dict:
+        b = table[t] if 0 <= t < len(table) else b""
+        return {"token": b.decode("utf-8", errors="replace"), "logprob": lp if math.isfinite(lp) else None,
+                "bytes": list(b)}
+
+    out = []
+    for t, (lp, top) in zip(ids, lps):
+        e = entry(int(t), float(lp))
+        e["top_logprobs"] = [entry(int(a), float(v)) for a, v in top if math.isfinite(v)]
+        out.append(e)
+    return out
 
 
 class StopFilter:

@@ -27,7 +27,7 @@ from ...utils import freeze_startup_objects
 from ...utils.metrics import METRICS
 from .protocol import (OLLAMA_VERSION, BadRequest, GenerateParams, StopFilter, apply_stop, chat_response,
                        stop_context_ids,
-                       final_fields, generate_response, now_iso)
+                       final_fields, generate_response, logprobs_field, now_iso)
 
 log = logging.getLogger("chronos.api")
 
@@ -59,6 +59,7 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
                 internal = (getattr(req, "meta", None) or {}).get("internal_error", False)
                 return web.json_response({"error": req.error}, status=500 if internal else 400)
             ctx = None
+            hit = False
             if params.stop:  # checked on the finished text: cut at the first stop string, reason "stop"
                 req.text, hit = apply_stop(req.text, params.stop)
                 if hit:
@@ -66,11 +67,18 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
                     tok = getattr(backend, "tok", None)
                     if tok is not None and not chat:
                         ctx = stop_context_ids(tok, req.prompt_ids, req.out_ids, req.text)
+            lps = None
+            if params.logprobs >= 0:
+                lps = logprobs_field(getattr(backend, "tok", None), req, req.text if hit else None)
+            lp_ignored = ("logprobs",) if params.logprobs >= 0 and lps is None else ()
             if chat:
-                return web.json_response(chat_response(model, req))
-            body = generate_response(model, req, params.ignored)
-            if ctx is not None:
-                body["context"] = ctx
+                body = chat_response(model, req, lp_ignored)
+            else:
+                body = generate_response(model, req, params.ignored + lp_ignored)
+                if ctx is not None:
+                    body["context"] = ctx
+            if lps is not None:
+                body["logprobs"] = lps
             return web.json_response(body)
         resp = web.StreamResponse(headers={"Content-Type": "application/x-ndjson"})
         await resp.prepare(request)
@@ -115,6 +123,12 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
                         chunk["response"] = ""
                         chunk["context"] = [int(t) for t in list(final.prompt_ids) + list(final.out_ids)]
                     chunk.update(final_fields(final))
+                    if params.logprobs >= 0:  # the whole list on the final chunk (protocol.py: deviation from Ollama)
+                        lps = logprobs_field(getattr(backend, "tok", None), final)
+                        if lps is None:
+                            chunk["ignored_options"] = ["logprobs"]
+                        else:
+                            chunk["logprobs"] = lps
             await resp.write((json.dumps(chunk) + "\n").encode())
         await resp.write_eof()
         return resp
@@ -237,6 +251,8 @@ def main(argv=None) -> int:
     ap.add_argument("--request-timeout", type=float, default=0.0,
                     help="seconds; a slower generation answers 504 and is cancelled in the engine (0 = none)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--max-logprobs", type=int, default=20,
+                    help="most top_logprobs a request may ask for (0-20); 0 = logprobs are not offered")
     ap.add_argument("--roctx", action="store_true", help="emit roctx ranges for rocprofv3 --marker-trace")
     a = ap.parse_args(argv)
     if a.roctx:
@@ -252,7 +268,8 @@ def main(argv=None) -> int:
 
         cfg = EngineConfig(model=a.model, checkpoint=a.checkpoint, tokenizer=a.tokenizer, device=a.device,
                            max_slots=a.max_slots, max_model_len=a.max_model_len, kv_dtype=a.kv_dtype,
-                           request_timeout_s=a.request_timeout, tp_sequence_parallel=a.sequence_parallel)
+                           request_timeout_s=a.request_timeout, tp_sequence_parallel=a.sequence_parallel,
+                           max_logprobs=a.max_logprobs)
         if a.tp > 1 or a.cp > 1:
             if a.tp > 1 and a.cp > 1:
                 raise SystemExit("--tp and --cp are exclusive (CP ranks hold full weights)")

@@ -115,7 +115,8 @@ class EngineService:
             handle["req"] = self.engine.submit(
                 ids, fmt=params.format, num_predict=params.num_predict, temperature=params.temperature,
                 seed=params.seed, top_k=params.top_k, top_p=params.top_p, callback=on_done,
-                meta={"on_tokens": on_tokens} if on_tokens else None, max_len=params.num_ctx or None)
+                meta={"on_tokens": on_tokens} if on_tokens else None, max_len=params.num_ctx or None,
+                logprobs=params.logprobs)
         elif kind == "cancel":
             req = item[1].get("req")
             if req is not None and not req.done_reason:
@@ -304,7 +305,8 @@ class LockstepService(EngineService):
                 return
             handle["tag"] = self.tpe.submit(ids, fmt=params.format, num_predict=params.num_predict,
                                             temperature=params.temperature, seed=params.seed, callback=on_done,
-                                            top_k=params.top_k, top_p=params.top_p, max_len=params.num_ctx or None)
+                                            top_k=params.top_k, top_p=params.top_p, max_len=params.num_ctx or None,
+                                            logprobs=params.logprobs)
         elif kind == "cancel":
             tag = item[1].get("tag")
             if tag is not None:

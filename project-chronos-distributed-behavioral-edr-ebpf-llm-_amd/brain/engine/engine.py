@@ -146,6 +146,14 @@ class EngineConfig:
     # token automata compiled at start-up (a first request must not pay the ~4 s vocab walk: the reference's cold-start
     # timeout): "verdict" = the CHRONOS verdict schema the sensor sends, "json" = format:"json"
     warm_formats: tuple = ("verdict", "json")
+    # Per-token logprobs (csrc/kernels/logprobs.hip): at most this many top alternatives per generated token (<= 20,
+    # Ollama's cap).  0 = the feature does not exist: no buffers, no launches, the decode graphs and their keys are
+    # what they were without it.  K > 0: the slot rings ([max_slots, max_out, 1 + K] f32 and [.., K] int32 on the
+    # device, two pinned host copies for the harvest) are allocated when the first request that asks starts decoding,
+    # and only launches with such a request running carry the two extra kernels (decode graphs: a second variant,
+    # captured on demand).  While any such request is running or starting, jump-forward is suppressed for the whole
+    # batch: a forced run appended by the host has no sampler step to take logprobs from.
+    max_logprobs: int = 0
 
 
 @dataclass
@@ -160,6 +168,7 @@ class Request:
     meta: dict = field(default_factory=dict)
     top_k: int = 0                 # 0 = off
     top_p: float = 1.0             # 1.0 = off
+    logprobs: int = -1             # -1 = off, 0 = the chosen token's logprob only, n = with the top n alternatives
     # runtime
     pending_text: Optional[tuple] = None  # (prompt, system, raw) until tokenized at admission
     slot: int = -1
@@ -167,6 +176,8 @@ class Request:
     prefilled: int = 0
     start_state: int = 0
     out_ids: list = field(default_factory=list)
+    # logprobs >= 0: one entry per id of out_ids, (logprob, [(token id, logprob), ...]) — see brain/api/protocol.py
+    out_logprobs: list = field(default_factory=list)
     text: str = ""
     done_reason: str = ""
     error: Optional[str] = None
@@ -178,6 +189,7 @@ class Request:
     # generated before a preemption (the re-prefilled prompt carries them), prompt length as submitted
     pos_hi: int = 0
     resume_out: list = field(default_factory=list)
+    resume_lp: list = field(default_factory=list)  # out_logprobs entries of resume_out
     orig_plen: int = -1
     preemptions: int = 0
 
@@ -213,6 +225,7 @@ class _Snapshot:
     out: torch.Tensor
     owners: dict
     seq: int = 0  # order in which snapshots were queued (a jump applied after snapshot k makes k's parked rows stale)
+    lp: Optional[tuple] = None  # (logprob ring [n, cols, 1 + K], id ring [n, cols, K]) when an owner wants logprobs
 
 
 class Engine:
@@ -294,6 +307,13 @@ class Engine:
         self.s_out = torch.zeros(S, cfg.max_out, **i32)
         self.s_bt = torch.zeros(S, self.max_blocks_per_seq, **i32)
         self.s_row = torch.full((S,), -1, **i32)
+        # per-token logprobs: allocated by _lp_alloc when the first request that wants them starts (None = never asked)
+        if not 0 <= cfg.max_logprobs <= ops.MAX_TOP_LOGPROBS:
+            raise ValueError(f"max_logprobs must be in 0..{ops.MAX_TOP_LOGPROBS}, not {cfg.max_logprobs}")
+        self.s_lp = self.s_lpids = self.s_lpwant = self.s_lpmark = self.s_lplse = None
+        self.s_lptid = self.s_lptval = None
+        self._snap_lp: Optional[list] = None  # third pinned pair of the harvest snapshots, allocated with the rings
+        self._starting: tuple | list = ()  # prompts whose first token the sampler launch being queued samples
         self.ar = torch.arange(S + 1, **i32)
         self.ar64 = torch.arange(S, dtype=torch.int64, device=dev)
         # ---- scheduling state ----
@@ -303,7 +323,8 @@ class Engine:
         self.running: dict[int, Request] = {}
         self.free_slots = list(range(S - 1, -1, -1))
         self._rid = itertools.count()
-        self._graphs: dict[tuple[int, int, int], torch.cuda.CUDAGraph] = {}  # (rows, kv splits, steps) -> graph
+        # (rows, kv splits, steps) -> graph; the variant with the logprob kernels: (rows, kv splits, steps, 1)
+        self._graphs: dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
         self.stats = collections.Counter()
         # host wall seconds per scheduler phase (harvest includes harvest_gpu_wait: the wait for the burst to finish)
@@ -338,13 +359,15 @@ class Engine:
     def submit(self, prompt: str | list, fmt=None, num_predict: int | None = None, temperature: float = 0.0,
                seed: int = 0, raw: bool = False, system: str | None = None,
                callback: Callable[[Request], None] | None = None, meta: dict | None = None, top_k: int = 0,
-               top_p: float = 1.0, max_len: int | None = None) -> Request:
+               top_p: float = 1.0, max_len: int | None = None, logprobs: int = -1) -> Request:
         """Queue a request.  A text prompt is tokenized (chat template) lazily at admission, a prefill chunk's worth
         at a time, so host tokenization of a large wave overlaps the GPU prefill of the previous chunk."""
         n = num_predict if num_predict and num_predict > 0 else self.cfg.default_num_predict
         req = Request(next(self._rid), prompt if isinstance(prompt, list) else [], fmt, min(n, self.cfg.max_out),
                       float(temperature or 0.0), int(seed or 0), callback, meta or {})
         req.top_k, req.top_p = int(top_k or 0), float(top_p if top_p is not None else 1.0)
+        if logprobs is not None and int(logprobs) >= 0 and self.cfg.max_logprobs > 0:
+            req.logprobs = min(int(logprobs), self.cfg.max_logprobs)
         if max_len:  # the request's own context window (Ollama options.num_ctx), within the engine's
             req.meta["max_len"] = min(int(max_len), self.cfg.max_model_len)
         req.t_submit = time.perf_counter()
@@ -658,12 +681,16 @@ class Engine:
         st = int(self.s_state[s].item())
         n = min(int(self.s_nout[s].item()), self.cfg.max_out)
         out = self.s_out[s, :n].tolist() if n else []
+        lps = []
+        if r.logprobs >= 0 and self.s_lp is not None and n:
+            lps = self._lp_entries(r, self.s_lp[s, :n].cpu(), self.s_lpids[s, :n].cpu(), n)
         del self.running[s]
         r.slot = -1
         self._free_slots([s])
         if st == DONE:  # finished on device, not harvested yet: complete it now
             stop = bool(out) and out[-1] in self.tok.stop_ids
             r.out_ids = r.resume_out + (out[:-1] if stop else out)
+            r.out_logprobs = r.resume_lp + (lps[:-1] if stop else lps)
             r.t_done = time.perf_counter()
             self.blocks.release(r.blocks)
             r.blocks = []
@@ -691,6 +718,7 @@ class Engine:
         r.blocks = []
         r.prompt_ids = ctx
         r.resume_out = r.resume_out + out
+        r.resume_lp = r.resume_lp + lps
         r.meta.setdefault("orig_num_predict", r.num_predict)
         r.num_predict -= n
         r.start_state = -2 - st if st <= -2 else st
@@ -813,6 +841,41 @@ class Engine:
         self.s_seed[sl] = dv(torch.tensor([r.seed for r in done_reqs], dtype=torch.int32))
         self.s_topk[sl] = dv(torch.tensor([r.top_k for r in done_reqs], dtype=torch.int32))
         self.s_topp[sl] = dv(torch.tensor([r.top_p for r in done_reqs], dtype=torch.float32))
+        if self.s_lp is None and any(r.logprobs >= 0 for r in done_reqs):
+            self._lp_alloc()
+        if self.s_lp is not None:
+            self.s_lpwant[sl] = dv(torch.tensor([r.logprobs for r in done_reqs], dtype=torch.int32))
+
+    # ---- per-token logprobs -----------------------------------------------------------------------------------------
+    def _lp_alloc(self) -> None:
+        S, K, mo, dev = self.cfg.max_slots, self.cfg.max_logprobs, self.cfg.max_out, self.device
+        self.s_lpwant = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.s_lpmark = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.s_lplse = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.s_lptid = torch.full((S, K), -1, dtype=torch.int32, device=dev)
+        self.s_lptval = torch.zeros(S, K, dtype=torch.float32, device=dev)
+        self.s_lpids = torch.full((S, mo, K), -1, dtype=torch.int32, device=dev)
+        self.s_lp = torch.zeros(S, mo, 1 + K, dtype=torch.float32, device=dev)
+        pin = dev.type == "cuda"
+        self._snap_lp = [(torch.zeros(S * mo * (1 + K), dtype=torch.float32, pin_memory=pin),
+                          torch.zeros(S * mo * K, dtype=torch.int32, pin_memory=pin)) for _ in range(2)]
+
+    def _lp_on(self) -> bool:
+        """Does a request that wants logprobs take part in the sampler launch about to be queued (running, or in
+        ``_starting``: the prompts whose first token that launch samples)?  False at once on an engine that was never
+        asked."""
+        if self.s_lp is None:
+            return False
+        return any(r.logprobs >= 0 for r in self.running.values()) or any(r.logprobs >= 0 for r in self._starting)
+
+    def _lp_entries(self, r: Request, lp, ids, k: int) -> list:
+        """Request.out_logprobs entries of ring rows lp [>= k, 1 + K], ids [>= k, K] (host arrays / tensors)."""
+        n = r.logprobs
+        out = []
+        for i in range(k):
+            row, rid = lp[i].tolist(), ids[i].tolist()
+            out.append((row[0], [(t, v) for t, v in zip(rid[:n], row[1:1 + n]) if t >= 0]))
+        return out
 
     def _start_running(self, done_reqs) -> None:
         now = time.perf_counter()
@@ -825,9 +888,19 @@ class Engine:
                 self.cancel(r, r.meta["cancel_reason"])
 
     def _sample(self, logits, jump) -> None:
+        """One sampler launch over the slots of ``s_row``; bracketed by the logprob kernels when a request that wants
+        them is running or starting in this launch (_lp_on)."""
+        lp = self._lp_on()
+        if lp:
+            ops.token_logprobs(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
+                               self.s_nout, self.s_lpwant, self.s_lpmark, self.s_lplse, self.s_lptid, self.s_lptval)
         ops.constrained_sample(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
                                self.s_temp, self.s_seed, self.s_ids, self.s_pos, self.s_ctx, self.s_nout, self.s_out,
                                self.s_topk, self.s_topp, jump)
+        if lp:
+            ops.token_logprobs_commit(logits, self.s_row, self.s_nout, self.s_out, self.s_lpwant, self.s_lpmark,
+                                      self.s_lplse, self.s_lptid, self.s_lptval, self.s_lp, self.s_lpids)
+            self.stats["logprob_launches"] += 1
 
     def _prefill_step(self) -> None:
         if self._copies:
@@ -859,8 +932,12 @@ class Engine:
         self.s_row.fill_(-1)
         self.s_row[h2d(torch.tensor([r.slot for r in done_reqs], dtype=torch.int64), self.device)] = h2d(
             torch.tensor(done_rows, dtype=torch.int32), self.device)
-        jf = self._jump_flags(len(self.running) + len(done_reqs))
-        self._sample(logits, jf)
+        self._starting = done_reqs
+        try:
+            jf = self._jump_flags(len(self.running) + len(done_reqs))
+            self._sample(logits, jf)
+        finally:
+            self._starting = ()
         self._check_parked = jf is not None
         self._start_running(done_reqs)
 
@@ -902,7 +979,11 @@ class Engine:
         if done_reqs:
             self.s_row[h2d(torch.tensor([r.slot for r in done_reqs], dtype=torch.int64), self.device)] = h2d(
                 torch.tensor(done_rows, dtype=torch.int32), self.device)
-        self._sample(logits, None)  # no jump-forward parking: this harvest lags one step
+        self._starting = done_reqs
+        try:
+            self._sample(logits, None)  # no jump-forward parking: this harvest lags one step
+        finally:
+            self._starting = ()
         self._start_running(done_reqs)
         self.stats["mixed_steps"] += 1
         self.stats["mixed_decode_rows"] += n
@@ -929,19 +1010,32 @@ class Engine:
     def _decode_rows(self) -> int:
         return _bucket(max(self.running) + 1) if self.running else 0
 
-    def _decode_once(self, n: int, nsplit: int) -> None:
+    def _decode_once(self, n: int, nsplit: int, lp: bool = False) -> None:
+        """One decode step of the first n slots.  ``lp``: a running request wants logprobs, so the sampler launch is
+        bracketed by the logprob kernels (and never parks: _jump_flags)."""
         sb = StepBatch(self.s_ids[:n], self.s_pos[:n], self.ar[:n], self.s_bt[:n], self.ar[:n + 1], self.s_ctx[:n],
                        self.ar64[:n], None, n, 1, nsplit, casc=self._casc)
         logits = self.model.forward(sb, self.kv)
+        if lp:
+            ops.token_logprobs(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
+                               self.s_nout[:n], self.s_lpwant[:n], self.s_lpmark[:n], self.s_lplse[:n],
+                               self.s_lptid[:n], self.s_lptval[:n])
         ops.constrained_sample(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
                                self.s_temp[:n], self.s_seed[:n], self.s_ids[:n], self.s_pos[:n], self.s_ctx[:n],
-                               self.s_nout[:n], self.s_out[:n], self.s_topk[:n], self.s_topp[:n], self._jump_flags(n))
+                               self.s_nout[:n], self.s_out[:n], self.s_topk[:n], self.s_topp[:n],
+                               None if lp else self._jump_flags(n))
+        if lp:
+            ops.token_logprobs_commit(logits, None, self.s_nout[:n], self.s_out[:n], self.s_lpwant[:n],
+                                      self.s_lpmark[:n], self.s_lplse[:n], self.s_lptid[:n], self.s_lptval[:n],
+                                      self.s_lp[:n], self.s_lpids[:n])
 
     def _jump_flags(self, rows: int):
         """The sampler's park-on-forced-run flags for a decode batch of ``rows`` sequences (None = never park).  With
         async harvest the snapshot a row parked in is read one burst late: the burst launched meanwhile runs that row
         gated (the sampler leaves parked rows untouched), the jump's device writes queue behind it, and the next
         snapshot — taken before the jump — is recognised as stale by the row's ``jump_seq`` (``_harvest``)."""
+        if self._lp_on():
+            return None  # a forced run appended by the host has no sampler step to take logprobs from
         if self.cfg.jump_forward and self.bank.jumps and 0 < rows <= self.cfg.jump_max_rows:
             return self.bank.jump
         return None
@@ -981,18 +1075,21 @@ class Engine:
         self._update_casc()
         n = min(self._decode_rows(), self.cfg.max_slots)
         ns = self._nsplit(n, self._ctx_class())
+        lp = self._lp_on()
         if self.device.type == "cuda" and self.cfg.use_graphs:
-            g = self._graphs.get((n, ns, k))
+            g = self._graphs.get((n, ns, k, 1) if lp else (n, ns, k))
             if g is None:
-                g = self._capture(n, ns, k)
+                g = self._capture(n, ns, k, lp)
             g.replay()
         else:
             self._gate(n)
             try:
                 for _ in range(k):
-                    self._decode_once(n, ns)
+                    self._decode_once(n, ns, lp)
             finally:
                 self._gate(0)
+        if lp:
+            self.stats["logprob_launches"] += k
         self.stats["decode_steps"] += k
         self.stats[f"bursts@{n}"] += 1
         self.stats["decode_row_steps"] += k * n
@@ -1008,11 +1105,22 @@ class Engine:
         st[:n].copy_(self.s_state[:n], non_blocking=True)
         no[:n].copy_(self.s_nout[:n], non_blocking=True)
         out[:n].copy_(self.s_out[:n], non_blocking=True)
+        lp = None
+        if self.s_lp is not None:
+            # the logprob rings of the rows and output columns in use, only while an owner wants them
+            cols = max((r.num_predict for r in self.running.values() if r.logprobs >= 0), default=0)
+            cols = min(cols, self.cfg.max_out)
+            if cols > 0:
+                K = self.cfg.max_logprobs
+                fl, fi = self._snap_lp[self._snap_i ^ 1]  # (_snap_i was flipped above: the buffers of st / no / out)
+                lp = (fl[:n * cols * (1 + K)].view(n, cols, 1 + K), fi[:n * cols * K].view(n, cols, K))
+                lp[0].copy_(self.s_lp[:n, :cols], non_blocking=True)
+                lp[1].copy_(self.s_lpids[:n, :cols], non_blocking=True)
         ev = None
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
             ev.record()
-        return _Snapshot(n, ev, st, no, out, dict(self.running), self._snap_seq)
+        return _Snapshot(n, ev, st, no, out, dict(self.running), self._snap_seq, lp)
 
     def _gate(self, n: int) -> None:
         """Arm the decode early-exit gate for a small bucket (n <= 8 rows): the steps of a burst after every row's
@@ -1020,7 +1128,7 @@ class Engine:
         if self.device.type == "cuda" and self.cfg.decode_gate:
             ops.set_decode_gate(self.s_state, n if 0 < n <= 8 else 0)
 
-    def _capture(self, n: int, ns: int, k: int) -> "torch.cuda.CUDAGraph":
+    def _capture(self, n: int, ns: int, k: int, lp: bool = False) -> "torch.cuda.CUDAGraph":
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
@@ -1029,10 +1137,10 @@ class Engine:
         try:
             with torch.cuda.graph(g, pool=self._graph_pool):
                 for _ in range(k):
-                    self._decode_once(n, ns)
+                    self._decode_once(n, ns, lp)
         finally:
             self._gate(0)
-        self._graphs[(n, ns, k)] = g
+        self._graphs[(n, ns, k, 1) if lp else (n, ns, k)] = g
         self.stats["graphs_captured"] += 1
         return g
 
@@ -1101,6 +1209,9 @@ class Engine:
             ids = ended[s] if s in ended else outs[s, :min(k, self.cfg.max_out)].tolist()
             stop = bool(ids) and ids[-1] in self.tok.stop_ids
             r.out_ids = r.resume_out + (ids[:-1] if stop else ids)
+            if r.logprobs >= 0 and snap.lp is not None and s not in ended:
+                # (the entry of a trailing stop token is dropped with the token)
+                r.out_logprobs = r.resume_lp + self._lp_entries(r, snap.lp[0][s], snap.lp[1][s], len(ids) - stop)
             r.t_done = now
             del self.running[r.slot]
             reset.append(r.slot)
@@ -1200,9 +1311,7 @@ class Engine:
             r.pos_hi = p + k + 1  # the run ends at p + k; the sampler's next token is written one past it
         self.s_row.fill_(-1)
         self.s_row[sl] = i32(list(range(len(rows))))
-        ops.constrained_sample(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
-                               self.s_temp, self.s_seed, self.s_ids, self.s_pos, self.s_ctx, self.s_nout, self.s_out,
-                               self.s_topk, self.s_topp, self._jump_flags(len(self.running)))
+        self._sample(logits, self._jump_flags(len(self.running)))
         self._check_parked = self._jump_flags(len(self.running)) is not None
         return ended
 
@@ -1222,8 +1331,11 @@ class Engine:
             return
         si = h2d(torch.tensor(movers, dtype=torch.int64), self.device)
         di = h2d(torch.tensor(dst, dtype=torch.int64), self.device)
+        lp = ()  # the logprob rings follow s_out (the want flags always: the target slot may hold a stale one)
+        if self.s_lp is not None:
+            lp = (self.s_lpwant, self.s_lp, self.s_lpids) if self._lp_on() else (self.s_lpwant,)
         for t in (self.s_ids, self.s_pos, self.s_ctx, self.s_state, self.s_rem, self.s_nout, self.s_seed, self.s_temp,
-                  self.s_topk, self.s_topp, self.s_out, self.s_bt):
+                  self.s_topk, self.s_topp, self.s_out, self.s_bt, *lp):
             t[di] = t[si]
         self.s_state.index_fill_(0, si, -1)
         self.s_bt.index_fill_(0, si, 0)
@@ -1245,6 +1357,7 @@ class Engine:
             req.num_predict = req.meta.pop("orig_num_predict", req.num_predict)
             if not req.out_ids and req.resume_out:
                 req.out_ids = list(req.resume_out)
+                req.out_logprobs = list(req.resume_lp)
         req.done_reason = reason
         if timed or not req.t_done:
             req.t_done = time.perf_counter()

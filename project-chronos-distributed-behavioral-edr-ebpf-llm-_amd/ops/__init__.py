@@ -4,7 +4,7 @@ There is no silent fallback on a GPU: a CUDA/HIP tensor always goes to ``torch.o
 extension (``_C*.so``, built by :mod:`chronos.native`) cannot be built or loaded the op raises.  CPU tensors (tests,
 the gloo-backed distributed tests, the CPU plumbing config) take :mod:`.reference`.
 
-Kernel sources: csrc/kernels/{elementwise,attention,sampler}.hip.
+Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs}.hip.
 """
 from __future__ import annotations
 
@@ -284,6 +284,68 @@ def constrained_sample(logits, row_of_slot, next_tab, dist, done_state: int, sta
     else:
         ref.constrained_sample(logits, row_of_slot, next_tab, dist, done_state, state, remaining, temperature, seed,
                                ids, pos, ctx, nout, out_tokens, topk, topp, jump)
+
+
+MAX_TOP_LOGPROBS = 20  # Ollama's top_logprobs cap; a compile-time bound of csrc/kernels/logprobs.hip
+
+
+def _check_logprobs(what: str, n: int, lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val, max_out=None, out_lp=None,
+                    out_lp_ids=None) -> None:
+    K = lp_top_ids.shape[1]
+    _need(K <= MAX_TOP_LOGPROBS, f"{what}: K = {K} exceeds {MAX_TOP_LOGPROBS}")
+    _need(min(lp_want.shape[0], lp_mark.shape[0], lp_lse.shape[0], lp_top_ids.shape[0], lp_top_val.shape[0]) >= n
+          and lp_top_val.shape[1] == K, f"{what}: scratch shapes")
+    if out_lp is not None:
+        _need(tuple(out_lp.shape[1:]) == (max_out, 1 + K) and tuple(out_lp_ids.shape[1:]) == (max_out, K)
+              and out_lp.shape[0] >= n and out_lp_ids.shape[0] >= n, f"{what}: ring shapes")
+        mk = lp_mark[:n].cpu().long()
+        _need(bool(((mk >= -1) & (mk <= max_out)).all()), f"{what}: lp_mark out of range")
+
+
+def token_logprobs(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, nout, lp_want, lp_mark,
+                   lp_lse, lp_top_ids, lp_top_val) -> None:
+    """Launched BEFORE ``constrained_sample`` on the same arguments: for every live slot with ``lp_want >= 0`` the
+    logsumexp of the legal tokens' raw logits (``lp_lse``), the K = ``lp_top_ids.shape[1]`` legal tokens with the
+    largest logits (``lp_top_ids`` / ``lp_top_val``: raw logits, logit descending then id ascending, tail -1 / -inf)
+    and ``lp_mark = nout``; every other slot gets ``lp_mark = -1`` (csrc/kernels/logprobs.hip)."""
+    if _checking(logits):
+        st = state.cpu().long()
+        S = next_tab.shape[0]
+        _need(bool(((st >= -1 - S) & (st < S)).all()), "token_logprobs: grammar state out of range")
+        _need(next_tab.shape[1] <= logits.shape[-1], "token_logprobs: grammar table wider than the logits")
+        if row_of_slot is not None:
+            rs = row_of_slot.cpu().long()
+            _need(bool(((rs >= -1) & (rs < logits.shape[0])).all()), "token_logprobs: logits row out of range")
+        else:
+            _need(state.shape[0] <= logits.shape[0], "token_logprobs: more slots than logits rows")
+        _check_logprobs("token_logprobs", state.shape[0], lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val)
+    if logits.is_cuda:
+        _k().token_logprobs(logits, row_of_slot, next_tab, dist, done_state, state, remaining, nout, lp_want, lp_mark,
+                            lp_lse, lp_top_ids, lp_top_val)
+    else:
+        ref.token_logprobs(logits, row_of_slot, next_tab, dist, done_state, state, remaining, nout, lp_want, lp_mark,
+                           lp_lse, lp_top_ids, lp_top_val)
+
+
+def token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val,
+                          out_lp, out_lp_ids) -> None:
+    """Launched AFTER ``constrained_sample``: where the sampler emitted output index ``i = lp_mark[slot]`` (``nout ==
+    i + 1``, ``i < max_out``) ring entry ``out_lp[slot, i] = [logprob(chosen), logprob(top 0), ...]`` and
+    ``out_lp_ids[slot, i] = top ids``.  Nothing else is written."""
+    if _checking(logits):
+        if row_of_slot is not None:
+            rs = row_of_slot.cpu().long()
+            _need(bool(((rs >= -1) & (rs < logits.shape[0])).all()), "token_logprobs_commit: logits row out of range")
+        else:
+            _need(nout.shape[0] <= logits.shape[0], "token_logprobs_commit: more slots than logits rows")
+        _check_logprobs("token_logprobs_commit", nout.shape[0], lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val,
+                        out_tokens.shape[1], out_lp, out_lp_ids)
+    if logits.is_cuda:
+        _k().token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mark, lp_lse, lp_top_ids,
+                                   lp_top_val, out_lp, out_lp_ids)
+    else:
+        ref.token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mark, lp_lse, lp_top_ids,
+                                  lp_top_val, out_lp, out_lp_ids)
 
 
 def attention_tiles(q_lens: list[int], hq: int, hkv: int, nqt: int) -> list[tuple[int, int]]:

@@ -235,3 +235,49 @@ def constrained_sample(logits, row_of_slot, next_tab, dist, done_state: int, sta
             ids[slot] = tok
             pos[slot] += 1
             ctx[slot] += 1
+
+
+def token_logprobs(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, nout, lp_want, lp_mark,
+                   lp_lse, lp_top_ids, lp_top_val) -> None:
+    """fp32 reference of csrc/kernels/logprobs.hip token_logprobs_kernel (host loop over the slots)."""
+    V, K = next_tab.shape[1], lp_top_ids.shape[1]
+    for slot in range(state.numel()):
+        s = int(state[slot])
+        row = -1 if (s < 0 or s == done_state) else (int(row_of_slot[slot]) if row_of_slot is not None else slot)
+        if row < 0 or int(lp_want[slot]) < 0:
+            lp_mark[slot] = -1
+            continue
+        nx = next_tab[s].long()
+        legal = (nx >= 0) & (dist[nx.clamp(min=0)].long() <= int(remaining[slot]) - 1)
+        idx = legal.nonzero().flatten()
+        if idx.numel() == 0:
+            lp_mark[slot] = -1
+            continue
+        x = logits[row, :V].float()[idx]
+        mx = float(x.max())
+        mx = 0.0 if mx == float("-inf") else mx
+        lp_lse[slot] = mx + float(torch.log(torch.exp(x - mx).sum()))
+        order = torch.sort(-(x + 0.0), stable=True).indices[:K]  # idx ascends, so equal logits keep id order
+        k = order.numel()
+        lp_top_ids[slot, :k] = idx[order].to(lp_top_ids.dtype)
+        lp_top_val[slot, :k] = x[order]
+        lp_top_ids[slot, k:] = -1
+        lp_top_val[slot, k:] = float("-inf")
+        lp_mark[slot] = int(nout[slot])
+
+
+def token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mark, lp_lse, lp_top_ids, lp_top_val,
+                          out_lp, out_lp_ids) -> None:
+    """fp32 reference of token_logprobs_commit_kernel."""
+    max_out = out_tokens.shape[1]
+    for slot in range(nout.numel()):
+        i = int(lp_mark[slot])
+        if i < 0 or i >= max_out or int(lp_want[slot]) < 0 or int(nout[slot]) != i + 1:
+            continue
+        row = int(row_of_slot[slot]) if row_of_slot is not None else slot
+        if row < 0:
+            continue
+        lse = lp_lse[slot]
+        out_lp[slot, i, 0] = logits[row, int(out_tokens[slot, i])].float() - lse
+        out_lp[slot, i, 1:] = lp_top_val[slot] - lse
+        out_lp_ids[slot, i] = lp_top_ids[slot]

@@ -7,6 +7,10 @@ HTTP, JSON) becomes ``{"risk_score": 0, "verdict": "ERROR", "reason": str(e)}``.
 :class:`BrainClient` is the blocking form (one chain in flight, as the reference).  :class:`AsyncBrainClient` fixes
 quirk Q1: many chains in flight over a pooled connection, optional retries with jittered backoff,
 and it can send the verdict JSON schema as ``format`` (Ollama structured outputs) instead of ``"json"``.
+
+``ClientConfig.confidence`` (sensor flag ``--confidence``) adds ``"logprobs": true`` to the request and stores the
+model's confidence in its verdict (sensor/confidence.py) in the result under ``CONFIDENCE_KEY``.  Off by default: the
+request body and the result are then exactly the reference's.
 """
 from __future__ import annotations
 
@@ -17,11 +21,13 @@ import time
 from dataclasses import dataclass
 from typing import Any, Sequence
 
+from .confidence import verdict_confidence
 from .prompt import VERDICT_SCHEMA, build_prompt
 
 DEFAULT_PORT = 11434
 DEFAULT_MODEL = "llama3"
 DEFAULT_TIMEOUT = 30.0
+CONFIDENCE_KEY = "_confidence"  # result key holding verdict_confidence(...) when ClientConfig.confidence is set
 
 
 def brain_url(host: str, port: int = DEFAULT_PORT) -> str:
@@ -43,13 +49,27 @@ class ClientConfig:
     retries: int = 0            # reference: no retry
     backoff: float = 0.25
     options: dict | None = None  # forwarded Ollama options (num_predict, temperature, seed, ...)
+    confidence: bool = False    # ask for logprobs and report the verdict's confidence
 
 
 def _body(cfg: ClientConfig, prompt: str) -> dict:
     body = {"model": cfg.model, "prompt": prompt, "stream": False, "format": cfg.fmt}
     if cfg.options:
         body["options"] = cfg.options
+    if cfg.confidence:
+        body["logprobs"] = True
     return body
+
+
+def _verdict(cfg: ClientConfig, data: dict) -> dict:
+    """The verdict of a reply body; with ``cfg.confidence`` also the model's confidence in it, when the Brain sent
+    logprobs (a Brain that cannot lists "logprobs" in ``ignored_options`` and the verdict stays as it is)."""
+    result = json.loads(data["response"])
+    if cfg.confidence and isinstance(result, dict):
+        conf = verdict_confidence(data["response"], data.get("logprobs"))
+        if conf is not None:
+            result[CONFIDENCE_KEY] = conf
+    return result
 
 
 class BrainClient:
@@ -65,7 +85,7 @@ class BrainClient:
         for attempt in range(self.cfg.retries + 1):
             try:
                 resp = self._session.post(self.cfg.url, json=_body(self.cfg, prompt), timeout=self.cfg.timeout)
-                return json.loads(resp.json()["response"])
+                return _verdict(self.cfg, resp.json())
             except Exception as e:  # noqa: BLE001 — the contract maps every failure to an ERROR verdict
                 last = e
                 if attempt < self.cfg.retries:
@@ -102,7 +122,7 @@ class AsyncBrainClient:
                     tmo = aiohttp.ClientTimeout(total=self.cfg.timeout)
                     async with sess.post(self.cfg.url, json=_body(self.cfg, prompt), timeout=tmo) as resp:
                         data = await resp.json(content_type=None)
-                    return json.loads(data["response"])
+                    return _verdict(self.cfg, data)
                 except Exception as e:  # noqa: BLE001
                     last = e
                     if attempt < self.cfg.retries:

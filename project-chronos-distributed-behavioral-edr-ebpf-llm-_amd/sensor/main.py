@@ -8,6 +8,7 @@ synthetic sources, the async many-in-flight client (quirk Q1), and the opt-in qu
   --source bcc | attack | replay:FILE | synthetic:N
   --async N                     keep up to N chains in flight (0 = blocking, reference)
   --fixed                       enable all quirk fixes (word triggers, bounded memory, distinct ERROR, strict filter)
+  --confidence                  ask the Brain for logprobs and print its confidence in each verdict
 """
 from __future__ import annotations
 
@@ -33,6 +34,8 @@ def _parse(argv=None):
     ap.add_argument("--async", dest="inflight", type=int, default=0)
     ap.add_argument("--fixed", action="store_true")
     ap.add_argument("--schema", action="store_true", help="send the verdict JSON schema as `format`")
+    ap.add_argument("--confidence", action="store_true",
+                    help="send logprobs: true and append the model's confidence in its verdict to the verdict line")
     ap.add_argument("--python-tracker", action="store_true", help="use the pure-Python tracker (oracle)")
     ap.add_argument("--page-cnt", type=int, default=64,
                     help="perf: pages per CPU ring (reference: 64); ringbuf: pages of the one shared ring")
@@ -121,7 +124,8 @@ def run(argv=None, src_factory=None) -> int:
     src_factory = src_factory or (lambda on_records: _kernel_source(on_records, args))
     url = _url(args.brain)
     ccfg = ClientConfig(url=url, model=args.model, timeout=args.timeout,
-                        fmt=schema_format() if args.schema else "json", retries=2 if args.fixed else 0)
+                        fmt=schema_format() if args.schema else "json", retries=2 if args.fixed else 0,
+                        confidence=args.confidence)
     render.emit([render.banner_connect(args.brain.split(":")[0])])
     tracker = _tracker(args)
     strict = args.fixed
@@ -132,7 +136,7 @@ def run(argv=None, src_factory=None) -> int:
         def handle(trig: Trigger):
             render.emit(render.chain_lines(trig.pid, trig.history) + [render.waiting_line(trig.pid)])
             result = client.analyze(trig.history)
-            render.emit(render.verdict_lines(result, distinct_errors=args.fixed))
+            render.emit(render.verdict_lines(result, distinct_errors=args.fixed, confidence=args.confidence))
 
         def on_records(buf: bytes, kernel_filter: bool):
             for trig in tracker.feed_records(buf, kernel_filter=kernel_filter, strict=strict):
@@ -161,7 +165,7 @@ def run(argv=None, src_factory=None) -> int:
             render.emit([render.banner_live()])
 
             def show(trig: Trigger, result: dict):
-                render.emit(render.chain_lines(trig.pid, trig.history) + render.verdict_lines(result, args.fixed))
+                render.emit(render.chain_lines(trig.pid, trig.history) + render.verdict_lines(result, args.fixed, args.confidence))
 
             try:
                 await live_async(src_factory, tracker, client.analyze, show, strict=strict)
@@ -177,7 +181,7 @@ def run(argv=None, src_factory=None) -> int:
 
         async def one(trig: Trigger):
             result = await client.analyze(trig.history)
-            render.emit(render.chain_lines(trig.pid, trig.history) + render.verdict_lines(result, args.fixed))
+            render.emit(render.chain_lines(trig.pid, trig.history) + render.verdict_lines(result, args.fixed, args.confidence))
             return result
 
         results = await asyncio.gather(*(one(t) for t in trigs))

@@ -3,6 +3,8 @@
 Compat mode reproduces the reference lines byte for byte, including quirk Q2 (an ERROR verdict has risk 0 and is
 printed as a green CLEAN line).  ``distinct_errors=True`` prints ERROR verdicts in yellow as ``ERROR`` instead.
 A non-numeric ``risk_score`` (quirk Q11: the reference raises inside the perf callback) is treated as 0 here.
+``confidence=True`` (sensor flag ``--confidence``) appends the model's confidence in its verdict to the verdict line
+when the result carries one; without it the lines are the reference's.
 """
 from __future__ import annotations
 
@@ -48,15 +50,17 @@ def is_alert(result: dict) -> bool:
     return risk_of(result) > ALERT_THRESHOLD
 
 
-def verdict_lines(result: dict, distinct_errors: bool = False) -> list[str]:
+def verdict_lines(result: dict, distinct_errors: bool = False, confidence: bool = False) -> list[str]:
     score = result.get("risk_score", 0)
     verdict = result.get("verdict")
     reason = result.get("reason")
+    conf = result.get("_confidence") if confidence else None  # sensor/client.py CONFIDENCE_KEY
+    tail = f" [confidence {100.0 * conf:.1f}%]" if isinstance(conf, float) else ""
     if distinct_errors and verdict == "ERROR":
         return [f"{YELLOW}    ==> ERROR: Brain unavailable (Risk {score}){RESET}", f"    ==> REASON: {reason}"]
     if is_alert(result):
-        return [f"{RED}    ==> ALERT: {verdict} (Risk {score}){RESET}", f"    ==> REASON: {reason}"]
-    return [f"{GREEN}    ==> CLEAN: {verdict} (Risk {score}){RESET}", f"    ==> REASON: {reason}"]
+        return [f"{RED}    ==> ALERT: {verdict} (Risk {score}){tail}{RESET}", f"    ==> REASON: {reason}"]
+    return [f"{GREEN}    ==> CLEAN: {verdict} (Risk {score}){tail}{RESET}", f"    ==> REASON: {reason}"]
 
 
 def emit(lines: Sequence[str], out: TextIO | None = None) -> None:
