@@ -44,6 +44,9 @@ void launch_token_logprobs(const void*, bool, int64_t, const int32_t*, int, int,
 void launch_token_logprobs_commit(const void*, bool, int64_t, int, const int32_t*, int, const int32_t*,
                                   const int32_t*, int, const int32_t*, const int32_t*, const float*, const int32_t*,
                                   const float*, int, float*, int32_t*, hipStream_t);
+void launch_apply_penalties(void*, bool, int64_t, int, const int32_t*, int, int, const int32_t*, const int32_t*,
+                            const int32_t*, int, const float*, const int32_t*, const int32_t*, const int32_t*, int,
+                            hipStream_t);
 void launch_gemv(const uint16_t*, int, int, const uint16_t*, int, uint16_t*, bool, hipStream_t);
 void attn_init();
 void launch_gemm(const uint16_t*, const uint16_t*, uint16_t*, int, int, int, bool, int, hipStream_t);
@@ -471,6 +474,37 @@ void token_logprobs_commit(const Tensor& logits, const c10::optional<Tensor>& ro
                                           i32(lp_want), i32(lp_mark), lp_lse.data_ptr<float>(), i32(lp_top_ids),
                                           lp_top_val.data_ptr<float>(), (int)K, out_lp.data_ptr<float>(),
                                           i32m(out_lp_ids), cur_stream());
+}
+
+// Repeat / frequency / presence penalties (csrc/kernels/penalties.hip): rewrites, in place and before the sampler, the
+// logits of the tokens in each live slot's history window.  pen_par f32 [slots, 3] = (repeat, frequency, presence),
+// pen_last int32 [slots] = window length L, pen_tail int32 [slots, W] / pen_tlen int32 [slots] = the prompt tail.
+void apply_penalties(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, int64_t done_state,
+                     const Tensor& state, const Tensor& nout, const Tensor& out_tokens, const Tensor& pen_par,
+                     const Tensor& pen_last, const Tensor& pen_tail, const Tensor& pen_tlen) {
+    chk_i32(state, "state");
+    const int64_t n = state.numel();
+    const int32_t* rp = chk_lp_rows(logits, row_of_slot, n);
+    CHK(logits.size(1) < (int64_t(1) << 31), "logits too wide");
+    chk_i32(nout, "nout");
+    CHK(nout.numel() >= n, "nout: one entry per slot");
+    chk_i32(out_tokens, "out_tokens");
+    CHK(out_tokens.dim() == 2 && out_tokens.size(0) >= n, "out_tokens [slots, max_out]");
+    chk_gpu(pen_par, "pen_par");
+    CHK(pen_par.scalar_type() == at::kFloat && pen_par.dim() == 2 && pen_par.size(0) >= n && pen_par.size(1) == 3,
+        "pen_par f32 [slots, 3]");
+    chk_i32(pen_last, "pen_last");
+    chk_i32(pen_tlen, "pen_tlen");
+    CHK(pen_last.numel() >= n && pen_tlen.numel() >= n, "pen_last / pen_tlen: one entry per slot");
+    chk_i32(pen_tail, "pen_tail");
+    CHK(pen_tail.dim() == 2 && pen_tail.size(0) >= n, "pen_tail int32 [slots, W]");
+    const int64_t W = pen_tail.size(1);
+    CHK(W >= 1 && W <= 1024, "penalty window W must be in 1..1024 (MAX_PENALTY_WINDOW)");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+    chronos::launch_apply_penalties(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0),
+                                    (int)logits.size(1), rp, (int)n, (int)done_state, i32(state), i32(nout),
+                                    i32(out_tokens), (int)out_tokens.size(1), pen_par.data_ptr<float>(), i32(pen_last),
+                                    i32(pen_tail), i32(pen_tlen), (int)W, cur_stream());
 }
 
 // y = x @ w.T for M <= 8 rows (decode); swiglu: w = [gate; up] -> y = silu(x@gate.T) * (x@up.T)
@@ -956,6 +990,8 @@ TORCH_LIBRARY(chronos, m) {
     m.def("token_logprobs_commit(Tensor logits, Tensor? row_of_slot, Tensor nout, Tensor out_tokens, Tensor lp_want, "
           "Tensor lp_mark, Tensor lp_lse, Tensor lp_top_ids, Tensor lp_top_val, Tensor(a!) out_lp, "
           "Tensor(b!) out_lp_ids) -> ()");
+    m.def("apply_penalties(Tensor(a!) logits, Tensor? row_of_slot, int done_state, Tensor state, Tensor nout, "
+          "Tensor out_tokens, Tensor pen_par, Tensor pen_last, Tensor pen_tail, Tensor pen_tlen) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
@@ -979,6 +1015,7 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("constrained_sample", &constrained_sample);
     m.impl("token_logprobs", &token_logprobs);
     m.impl("token_logprobs_commit", &token_logprobs_commit);
+    m.impl("apply_penalties", &apply_penalties);
     m.impl("ar_all_reduce", &ar_all_reduce);
     m.impl("ar_all_reduce_norm", &ar_all_reduce_norm);
 }

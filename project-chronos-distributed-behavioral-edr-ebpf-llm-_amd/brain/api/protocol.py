@@ -10,8 +10,17 @@ stream=true NDJSON, timing fields in ns) and /api/chat are served too so any Oll
   prompt that does not fit is a 400, ``num_predict`` is clamped to what is left;
 * ``context`` (request) continues from a previous reply's ``context`` (returned: prompt + generated token ids);
 * ``keep_alive`` is accepted; the weights stay resident regardless (warm at start-up, quirk X8);
-* ``options.repeat_penalty`` / ``frequency_penalty`` / ``presence_penalty`` are accepted and not applied (the
-  verdict sampler is grammar-constrained greedy; a penalty != 1 / 0 is reported in the reply's ``ignored_options``).
+* ``options.repeat_penalty`` / ``frequency_penalty`` / ``presence_penalty`` / ``repeat_last_n`` are llama.cpp's
+  penalties, applied on the device inside the decode step (csrc/kernels/penalties.hip).  At every sampler step the
+  history is the last ``repeat_last_n`` tokens of the prompt followed by everything generated so far (grammar-forced
+  tokens included); each distinct token ``v`` of it with count ``c`` gets ``x = logit[v]; x = x * repeat_penalty if
+  x <= 0 else x / repeat_penalty; x -= c * frequency_penalty + presence_penalty``.  Legality (``format``, budget
+  forcing) is not affected: a forced token stays forced.  The defaults are neutral (1 / 0 / 0) — Ollama's own default
+  ``repeat_penalty`` of 1.1 is deliberately NOT applied, so a request that names no penalty decodes as it always did.
+  ``repeat_last_n`` defaults to 64; 0 switches the penalties off for the request; -1 means as far back as the engine
+  keeps; any value above the engine's window (``--penalty-window``, EngineConfig.penalty_window, at most 1024) is
+  clamped to that window.  A backend that cannot apply them (server started with ``--penalty-window 0``, the fake
+  backend) answers normally, unpenalised, and names each penalty that is not neutral in ``ignored_options``.
 
 Per-token logprobs (``"logprobs": true`` and optionally ``"top_logprobs": n``, 0 <= n <= 20, both top-level, for
 generate and chat).  The reply gains ``"logprobs": [{"token", "logprob", "bytes", "top_logprobs": [{"token",
@@ -21,7 +30,9 @@ token sampled at output index i (csrc/kernels/logprobs.hip computes them on the 
 * the *legal set* is exactly the sampler's: tokens the request's grammar (``format``) allows in its current state and
   that still let the output close within ``num_predict`` (budget forcing);
 * ``logprob(v) = logit[v] - logsumexp(logit[u] for legal u)``: raw logits, natural log, temperature 1, taken BEFORE
-  any top-k / top-p truncation — whatever the request's temperature, top_k or top_p.  A token the grammar forces (one
+  any top-k / top-p truncation but AFTER the request's penalties (above): the penalty kernel runs first, the logprob
+  kernels and the sampler both see the penalised row, so a request that asks for both gets the logprobs of the
+  distribution its token was actually drawn from — whatever the request's temperature, top_k or top_p.  A token the grammar forces (one
   legal token) has logprob exactly 0.0; without a ``format`` this is the ordinary log-softmax (up to budget forcing
   near ``num_predict``);
 * ``top_logprobs`` lists the n legal tokens with the largest logits, ordered by logit descending, then token id
@@ -46,6 +57,15 @@ from typing import Any, Optional
 
 OLLAMA_VERSION = "0.5.7-chronos"
 MAX_TOP_LOGPROBS = 20  # Ollama's cap on top_logprobs (and the kernels': chronos.ops.MAX_TOP_LOGPROBS)
+PENALTY_NEUTRAL = (("repeat_penalty", 1.0), ("frequency_penalty", 0.0), ("presence_penalty", 0.0))
+
+
+def _number(opts: dict, key: str, default: float) -> float:
+    """options[key] as a finite float (a 400 that names the option otherwise)."""
+    v = opts.get(key, default)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+        raise BadRequest(f"options.{key} must be a finite number")
+    return float(v)
 
 
 class BadRequest(ValueError):
@@ -70,7 +90,13 @@ class GenerateParams:
     num_ctx: int = 0
     context: Optional[list] = None
     keep_alive: Any = None
+    # the penalties that are not neutral (none with repeat_last_n 0): reported in ``ignored_options`` by a backend
+    # that did not apply them (penalties_ignored)
     ignored: tuple = ()
+    repeat_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    repeat_last_n: int = 64
     logprobs: int = -1  # -1 = not asked, 0 = the generated tokens' logprobs, n = with the top n alternatives
 
     @classmethod
@@ -122,9 +148,17 @@ class GenerateParams:
                 raise BadRequest("top_logprobs requires logprobs: true")
         if lp:
             p.logprobs = int(top or 0)
-        p.ignored = tuple(k for k, neutral in (("repeat_penalty", 1.0), ("frequency_penalty", 0.0),
-                                               ("presence_penalty", 0.0))
-                          if k in opts and float(opts[k]) != neutral)
+        p.repeat_penalty = _number(opts, "repeat_penalty", 1.0)
+        if p.repeat_penalty <= 0:
+            raise BadRequest("options.repeat_penalty must be greater than 0")
+        p.frequency_penalty = _number(opts, "frequency_penalty", 0.0)
+        p.presence_penalty = _number(opts, "presence_penalty", 0.0)
+        last = opts.get("repeat_last_n", 64)
+        if isinstance(last, bool) or not isinstance(last, int) or last < -1:
+            raise BadRequest("options.repeat_last_n must be an integer of at least -1")
+        p.repeat_last_n = last
+        if last != 0:
+            p.ignored = tuple(k for k, neutral in PENALTY_NEUTRAL if getattr(p, k) != neutral)
         if chat:
             msgs = body.get("messages")
             if not isinstance(msgs, list) or not msgs:
@@ -169,6 +203,12 @@ def final_fields(req, load_duration: float = 0.0) -> dict:
         "eval_count": len(req.out_ids),
         "eval_duration": _ns(req.t_done - first),
     }
+
+
+def penalties_ignored(params: GenerateParams, req) -> tuple:
+    """The penalty options of ``params`` to report in ``ignored_options``: its non-neutral ones when the backend did
+    not apply them (a finished engine request carries ``penalty``, a tuple, exactly when its engine did)."""
+    return () if getattr(req, "penalty", None) else params.ignored
 
 
 def generate_response(model: str, req, ignored: tuple = ()) -> dict:

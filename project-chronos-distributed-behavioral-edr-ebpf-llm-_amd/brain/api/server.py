@@ -27,7 +27,7 @@ from ...utils import freeze_startup_objects
 from ...utils.metrics import METRICS
 from .protocol import (OLLAMA_VERSION, BadRequest, GenerateParams, StopFilter, apply_stop, chat_response,
                        stop_context_ids,
-                       final_fields, generate_response, logprobs_field, now_iso)
+                       final_fields, generate_response, logprobs_field, now_iso, penalties_ignored)
 
 log = logging.getLogger("chronos.api")
 
@@ -70,11 +70,11 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
             lps = None
             if params.logprobs >= 0:
                 lps = logprobs_field(getattr(backend, "tok", None), req, req.text if hit else None)
-            lp_ignored = ("logprobs",) if params.logprobs >= 0 and lps is None else ()
+            ignored = penalties_ignored(params, req) + (("logprobs",) if params.logprobs >= 0 and lps is None else ())
             if chat:
-                body = chat_response(model, req, lp_ignored)
+                body = chat_response(model, req, ignored)
             else:
-                body = generate_response(model, req, params.ignored + lp_ignored)
+                body = generate_response(model, req, ignored)
                 if ctx is not None:
                     body["context"] = ctx
             if lps is not None:
@@ -123,12 +123,15 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
                         chunk["response"] = ""
                         chunk["context"] = [int(t) for t in list(final.prompt_ids) + list(final.out_ids)]
                     chunk.update(final_fields(final))
+                    ignored = penalties_ignored(params, final)
                     if params.logprobs >= 0:  # the whole list on the final chunk (protocol.py: deviation from Ollama)
                         lps = logprobs_field(getattr(backend, "tok", None), final)
                         if lps is None:
-                            chunk["ignored_options"] = ["logprobs"]
+                            ignored += ("logprobs",)
                         else:
                             chunk["logprobs"] = lps
+                    if ignored:
+                        chunk["ignored_options"] = list(ignored)
             await resp.write((json.dumps(chunk) + "\n").encode())
         await resp.write_eof()
         return resp
@@ -253,6 +256,9 @@ def main(argv=None) -> int:
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--max-logprobs", type=int, default=20,
                     help="most top_logprobs a request may ask for (0-20); 0 = logprobs are not offered")
+    ap.add_argument("--penalty-window", type=int, default=64,
+                    help="history window of repeat / frequency / presence penalties, the most repeat_last_n can "
+                         "reach (0-1024); 0 = penalties are not offered")
     ap.add_argument("--roctx", action="store_true", help="emit roctx ranges for rocprofv3 --marker-trace")
     a = ap.parse_args(argv)
     if a.roctx:
@@ -269,7 +275,7 @@ def main(argv=None) -> int:
         cfg = EngineConfig(model=a.model, checkpoint=a.checkpoint, tokenizer=a.tokenizer, device=a.device,
                            max_slots=a.max_slots, max_model_len=a.max_model_len, kv_dtype=a.kv_dtype,
                            request_timeout_s=a.request_timeout, tp_sequence_parallel=a.sequence_parallel,
-                           max_logprobs=a.max_logprobs)
+                           max_logprobs=a.max_logprobs, penalty_window=a.penalty_window)
         if a.tp > 1 or a.cp > 1:
             if a.tp > 1 and a.cp > 1:
                 raise SystemExit("--tp and --cp are exclusive (CP ranks hold full weights)")

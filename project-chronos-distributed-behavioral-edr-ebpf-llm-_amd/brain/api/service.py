@@ -116,7 +116,9 @@ class EngineService:
                 ids, fmt=params.format, num_predict=params.num_predict, temperature=params.temperature,
                 seed=params.seed, top_k=params.top_k, top_p=params.top_p, callback=on_done,
                 meta={"on_tokens": on_tokens} if on_tokens else None, max_len=params.num_ctx or None,
-                logprobs=params.logprobs)
+                logprobs=params.logprobs, repeat_penalty=params.repeat_penalty,
+                frequency_penalty=params.frequency_penalty, presence_penalty=params.presence_penalty,
+                repeat_last_n=params.repeat_last_n)
         elif kind == "cancel":
             req = item[1].get("req")
             if req is not None and not req.done_reason:
@@ -306,7 +308,10 @@ class LockstepService(EngineService):
             handle["tag"] = self.tpe.submit(ids, fmt=params.format, num_predict=params.num_predict,
                                             temperature=params.temperature, seed=params.seed, callback=on_done,
                                             top_k=params.top_k, top_p=params.top_p, max_len=params.num_ctx or None,
-                                            logprobs=params.logprobs)
+                                            logprobs=params.logprobs, repeat_penalty=params.repeat_penalty,
+                                            frequency_penalty=params.frequency_penalty,
+                                            presence_penalty=params.presence_penalty,
+                                            repeat_last_n=params.repeat_last_n)
         elif kind == "cancel":
             tag = item[1].get("tag")
             if tag is not None:

@@ -154,6 +154,15 @@ class EngineConfig:
     # captured on demand).  While any such request is running or starting, jump-forward is suppressed for the whole
     # batch: a forced run appended by the host has no sampler step to take logprobs from.
     max_logprobs: int = 0
+    # Repeat / frequency / presence penalties (csrc/kernels/penalties.hip): the history window W the engine keeps per
+    # slot, 0..1024 — the last W prompt ids (a [max_slots, W] int32 device buffer) plus the slot's own output ring.
+    # 0 = the feature does not exist: no buffers, no launches, the decode graphs and their keys are what they were
+    # without it, and a submit that names penalties is accepted but decodes unpenalised (``Engine.can_penalise``).
+    # W > 0: the buffers are allocated when the first penalised request starts decoding, only launches with such a
+    # request running or starting carry the penalty kernel (decode graphs: a further variant, captured on demand), and
+    # a request's repeat_last_n above W is clamped to W.  Jump-forward stays on: forced runs enter the history through
+    # the output ring.
+    penalty_window: int = 0
 
 
 @dataclass
@@ -169,6 +178,9 @@ class Request:
     top_k: int = 0                 # 0 = off
     top_p: float = 1.0             # 1.0 = off
     logprobs: int = -1             # -1 = off, 0 = the chosen token's logprob only, n = with the top n alternatives
+    # (repeat_penalty, frequency_penalty, presence_penalty, window length L in 1..penalty_window) of a request the
+    # engine penalises; None = neutral parameters, repeat_last_n 0, or an engine with penalty_window 0
+    penalty: Optional[tuple] = None
     # runtime
     pending_text: Optional[tuple] = None  # (prompt, system, raw) until tokenized at admission
     slot: int = -1
@@ -235,6 +247,8 @@ class Engine:
         run this engine in lockstep (same submissions, same order); long prefill chunks are split across them and
         each prefill step covers ``max_prefill_tokens`` per rank."""
         self.cfg = cfg
+        if not 0 <= cfg.penalty_window <= ops.MAX_PENALTY_WINDOW:
+            raise ValueError(f"penalty_window must be in 0..{ops.MAX_PENALTY_WINDOW}, not {cfg.penalty_window}")
         self.tp = tp or TPContext.single()
         self.cp = cp or TPContext.single()
         if self.cp.world > 1 and self.tp.world > 1:
@@ -314,6 +328,8 @@ class Engine:
         self.s_lptid = self.s_lptval = None
         self._snap_lp: Optional[list] = None  # third pinned pair of the harvest snapshots, allocated with the rings
         self._starting: tuple | list = ()  # prompts whose first token the sampler launch being queued samples
+        # penalties: allocated by _pen_alloc when the first penalised request starts (None = never asked)
+        self.s_penpar = self.s_penlast = self.s_pentail = self.s_pentlen = None
         self.ar = torch.arange(S + 1, **i32)
         self.ar64 = torch.arange(S, dtype=torch.int64, device=dev)
         # ---- scheduling state ----
@@ -323,7 +339,8 @@ class Engine:
         self.running: dict[int, Request] = {}
         self.free_slots = list(range(S - 1, -1, -1))
         self._rid = itertools.count()
-        # (rows, kv splits, steps) -> graph; the variant with the logprob kernels: (rows, kv splits, steps, 1)
+        # (rows, kv splits, steps) -> graph; the variant with the logprob kernels: (rows, kv splits, steps, 1); the
+        # variants with the penalty kernel: (rows, kv splits, steps, 0 or 1 for the logprob kernels, "pen") — _gkey
         self._graphs: dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
         self.stats = collections.Counter()
@@ -359,15 +376,25 @@ class Engine:
     def submit(self, prompt: str | list, fmt=None, num_predict: int | None = None, temperature: float = 0.0,
                seed: int = 0, raw: bool = False, system: str | None = None,
                callback: Callable[[Request], None] | None = None, meta: dict | None = None, top_k: int = 0,
-               top_p: float = 1.0, max_len: int | None = None, logprobs: int = -1) -> Request:
+               top_p: float = 1.0, max_len: int | None = None, logprobs: int = -1, repeat_penalty: float = 1.0,
+               frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64) -> Request:
         """Queue a request.  A text prompt is tokenized (chat template) lazily at admission, a prefill chunk's worth
-        at a time, so host tokenization of a large wave overlaps the GPU prefill of the previous chunk."""
+        at a time, so host tokenization of a large wave overlaps the GPU prefill of the previous chunk.
+
+        Penalties (llama.cpp's): neutral by default; ``repeat_last_n`` 0 = off, -1 = the engine's whole window, above
+        ``penalty_window`` = clamped to it.  An engine with ``penalty_window`` 0 accepts and does not apply them."""
         n = num_predict if num_predict and num_predict > 0 else self.cfg.default_num_predict
         req = Request(next(self._rid), prompt if isinstance(prompt, list) else [], fmt, min(n, self.cfg.max_out),
                       float(temperature or 0.0), int(seed or 0), callback, meta or {})
         req.top_k, req.top_p = int(top_k or 0), float(top_p if top_p is not None else 1.0)
         if logprobs is not None and int(logprobs) >= 0 and self.cfg.max_logprobs > 0:
             req.logprobs = min(int(logprobs), self.cfg.max_logprobs)
+        rp = 1.0 if repeat_penalty is None else float(repeat_penalty)
+        fq, pr = float(frequency_penalty or 0.0), float(presence_penalty or 0.0)
+        last = 64 if repeat_last_n is None else int(repeat_last_n)
+        if self.cfg.penalty_window > 0 and last != 0 and (rp != 1.0 or fq != 0.0 or pr != 0.0):
+            W = self.cfg.penalty_window
+            req.penalty = (rp, fq, pr, W if last < 0 else min(last, W))
         if max_len:  # the request's own context window (Ollama options.num_ctx), within the engine's
             req.meta["max_len"] = min(int(max_len), self.cfg.max_model_len)
         req.t_submit = time.perf_counter()
@@ -845,6 +872,49 @@ class Engine:
             self._lp_alloc()
         if self.s_lp is not None:
             self.s_lpwant[sl] = dv(torch.tensor([r.logprobs for r in done_reqs], dtype=torch.int32))
+        if self.s_penpar is None and any(r.penalty for r in done_reqs):
+            self._pen_alloc()
+        if self.s_penpar is not None:
+            # every slot that starts gets its parameters (a reused slot may hold a penalised request's); the prompt
+            # tail — the last W ids of the sequence that was prefilled, which after a preemption is the prompt plus the
+            # output generated before it — only when one of them is penalised
+            self.s_penpar[sl] = dv(torch.tensor([(r.penalty or (1.0, 0.0, 0.0))[:3] for r in done_reqs],
+                                                dtype=torch.float32))
+            self.s_penlast[sl] = dv(torch.tensor([r.penalty[3] if r.penalty else 0 for r in done_reqs],
+                                                 dtype=torch.int32))
+            if any(r.penalty for r in done_reqs):
+                W = self.cfg.penalty_window
+                tails = [r.prompt_ids[-W:] if r.penalty else [] for r in done_reqs]
+                self.s_pentail[sl] = dv(torch.tensor([t + [-1] * (W - len(t)) for t in tails], dtype=torch.int32))
+                self.s_pentlen[sl] = dv(torch.tensor([len(t) for t in tails], dtype=torch.int32))
+
+    # ---- penalties --------------------------------------------------------------------------------------------------
+    @property
+    def can_penalise(self) -> bool:
+        """Does this engine apply repeat / frequency / presence penalties (EngineConfig.penalty_window > 0)?"""
+        return self.cfg.penalty_window > 0
+
+    def _pen_alloc(self) -> None:
+        S, W, dev = self.cfg.max_slots, self.cfg.penalty_window, self.device
+        self.s_penpar = torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32, device=dev).repeat(S, 1)
+        self.s_penlast = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.s_pentail = torch.full((S, W), -1, dtype=torch.int32, device=dev)
+        self.s_pentlen = torch.zeros(S, dtype=torch.int32, device=dev)
+
+    def _pen_on(self) -> bool:
+        """Does a penalised request take part in the sampler launch about to be queued (running, or in ``_starting``)?
+        False at once on an engine that was never asked."""
+        if self.s_penpar is None:
+            return False
+        return any(r.penalty for r in self.running.values()) or any(r.penalty for r in self._starting)
+
+    @staticmethod
+    def _gkey(n: int, ns: int, k: int, lp: bool, pen: bool) -> tuple:
+        """Decode-graph key: (n, ns, k), with the logprob kernels (n, ns, k, 1), with the penalty kernel
+        (n, ns, k, 0 or 1, "pen")."""
+        if pen:
+            return (n, ns, k, int(lp), "pen")
+        return (n, ns, k, 1) if lp else (n, ns, k)
 
     # ---- per-token logprobs -----------------------------------------------------------------------------------------
     def _lp_alloc(self) -> None:
@@ -889,7 +959,12 @@ class Engine:
 
     def _sample(self, logits, jump) -> None:
         """One sampler launch over the slots of ``s_row``; bracketed by the logprob kernels when a request that wants
-        them is running or starting in this launch (_lp_on)."""
+        them is running or starting in this launch (_lp_on), preceded by the penalty kernel when a penalised one is
+        (_pen_on): the logprob kernels and the sampler both see the penalised rows."""
+        if self._pen_on():
+            ops.apply_penalties(logits, self.s_row, DONE, self.s_state, self.s_nout, self.s_out, self.s_penpar,
+                                self.s_penlast, self.s_pentail, self.s_pentlen)
+            self.stats["penalty_launches"] += 1
         lp = self._lp_on()
         if lp:
             ops.token_logprobs(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
@@ -1010,12 +1085,16 @@ class Engine:
     def _decode_rows(self) -> int:
         return _bucket(max(self.running) + 1) if self.running else 0
 
-    def _decode_once(self, n: int, nsplit: int, lp: bool = False) -> None:
+    def _decode_once(self, n: int, nsplit: int, lp: bool = False, pen: bool = False) -> None:
         """One decode step of the first n slots.  ``lp``: a running request wants logprobs, so the sampler launch is
-        bracketed by the logprob kernels (and never parks: _jump_flags)."""
+        bracketed by the logprob kernels (and never parks: _jump_flags).  ``pen``: a running request is penalised, so
+        the penalty kernel rewrites the logits first."""
         sb = StepBatch(self.s_ids[:n], self.s_pos[:n], self.ar[:n], self.s_bt[:n], self.ar[:n + 1], self.s_ctx[:n],
                        self.ar64[:n], None, n, 1, nsplit, casc=self._casc)
         logits = self.model.forward(sb, self.kv)
+        if pen:
+            ops.apply_penalties(logits, None, DONE, self.s_state[:n], self.s_nout[:n], self.s_out[:n],
+                                self.s_penpar[:n], self.s_penlast[:n], self.s_pentail[:n], self.s_pentlen[:n])
         if lp:
             ops.token_logprobs(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
                                self.s_nout[:n], self.s_lpwant[:n], self.s_lpmark[:n], self.s_lplse[:n],
@@ -1075,21 +1154,23 @@ class Engine:
         self._update_casc()
         n = min(self._decode_rows(), self.cfg.max_slots)
         ns = self._nsplit(n, self._ctx_class())
-        lp = self._lp_on()
+        lp, pen = self._lp_on(), self._pen_on()
         if self.device.type == "cuda" and self.cfg.use_graphs:
-            g = self._graphs.get((n, ns, k, 1) if lp else (n, ns, k))
+            g = self._graphs.get(self._gkey(n, ns, k, lp, pen))
             if g is None:
-                g = self._capture(n, ns, k, lp)
+                g = self._capture(n, ns, k, lp, pen)
             g.replay()
         else:
             self._gate(n)
             try:
                 for _ in range(k):
-                    self._decode_once(n, ns, lp)
+                    self._decode_once(n, ns, lp, pen)
             finally:
                 self._gate(0)
         if lp:
             self.stats["logprob_launches"] += k
+        if pen:
+            self.stats["penalty_launches"] += k
         self.stats["decode_steps"] += k
         self.stats[f"bursts@{n}"] += 1
         self.stats["decode_row_steps"] += k * n
@@ -1128,7 +1209,7 @@ class Engine:
         if self.device.type == "cuda" and self.cfg.decode_gate:
             ops.set_decode_gate(self.s_state, n if 0 < n <= 8 else 0)
 
-    def _capture(self, n: int, ns: int, k: int, lp: bool = False) -> "torch.cuda.CUDAGraph":
+    def _capture(self, n: int, ns: int, k: int, lp: bool = False, pen: bool = False) -> "torch.cuda.CUDAGraph":
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
@@ -1137,10 +1218,10 @@ class Engine:
         try:
             with torch.cuda.graph(g, pool=self._graph_pool):
                 for _ in range(k):
-                    self._decode_once(n, ns, lp)
+                    self._decode_once(n, ns, lp, pen)
         finally:
             self._gate(0)
-        self._graphs[(n, ns, k, 1) if lp else (n, ns, k)] = g
+        self._graphs[self._gkey(n, ns, k, lp, pen)] = g
         self.stats["graphs_captured"] += 1
         return g
 
@@ -1334,6 +1415,10 @@ class Engine:
         lp = ()  # the logprob rings follow s_out (the want flags always: the target slot may hold a stale one)
         if self.s_lp is not None:
             lp = (self.s_lpwant, self.s_lp, self.s_lpids) if self._lp_on() else (self.s_lpwant,)
+        if self.s_penpar is not None:  # likewise the penalty parameters always, the prompt tails while one is penalised
+            lp += (self.s_penpar, self.s_penlast)
+            if self._pen_on():
+                lp += (self.s_pentail, self.s_pentlen)
         for t in (self.s_ids, self.s_pos, self.s_ctx, self.s_state, self.s_rem, self.s_nout, self.s_seed, self.s_temp,
                   self.s_topk, self.s_topp, self.s_out, self.s_bt, *lp):
             t[di] = t[si]

@@ -4,7 +4,7 @@ There is no silent fallback on a GPU: a CUDA/HIP tensor always goes to ``torch.o
 extension (``_C*.so``, built by :mod:`chronos.native`) cannot be built or loaded the op raises.  CPU tensors (tests,
 the gloo-backed distributed tests, the CPU plumbing config) take :mod:`.reference`.
 
-Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs}.hip.
+Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties}.hip.
 """
 from __future__ import annotations
 
@@ -346,6 +346,42 @@ def token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mar
     else:
         ref.token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mark, lp_lse, lp_top_ids,
                                   lp_top_val, out_lp, out_lp_ids)
+
+
+MAX_PENALTY_WINDOW = 1024  # a compile-time bound of csrc/kernels/penalties.hip (its LDS history window)
+
+
+def apply_penalties(logits, row_of_slot, done_state: int, state, nout, out_tokens, pen_par, pen_last, pen_tail,
+                    pen_tlen) -> None:
+    """Launched BEFORE ``token_logprobs`` / ``constrained_sample`` on the same logits: llama.cpp's repeat, frequency
+    and presence penalties, in place.  For every live slot (the sampler's test and row addressing) whose
+    ``pen_par[slot] = (repeat, frequency, presence)`` is not the neutral (1, 0, 0) and whose window ``pen_last[slot]``
+    is > 0, the history is ``pen_tail[slot, :pen_tlen[slot]]`` (the last <= W prompt ids) followed by
+    ``out_tokens[slot, :nout[slot]]``, cut to its last ``pen_last`` entries; each distinct token ``v`` of it with count
+    ``c`` gets ``x = logit[v]; x = x * rp if x <= 0 else x / rp; x -= c * fq + pr`` in fp32, written back in the
+    row's dtype.  No other logit is touched (csrc/kernels/penalties.hip)."""
+    if _checking(logits):
+        n = state.shape[0]
+        if row_of_slot is not None:
+            rs = row_of_slot.cpu().long()
+            _need(row_of_slot.shape[0] >= n, "apply_penalties: row_of_slot shorter than the slots")
+            _need(bool(((rs >= -1) & (rs < logits.shape[0])).all()), "apply_penalties: logits row out of range")
+        else:
+            _need(n <= logits.shape[0], "apply_penalties: more slots than logits rows")
+        W = pen_tail.shape[1]
+        _need(1 <= W <= MAX_PENALTY_WINDOW, f"apply_penalties: window {W} outside 1..{MAX_PENALTY_WINDOW}")
+        _need(min(nout.shape[0], out_tokens.shape[0], pen_par.shape[0], pen_last.shape[0], pen_tail.shape[0],
+                  pen_tlen.shape[0]) >= n and pen_par.shape[1] == 3, "apply_penalties: per-slot shapes")
+        tl = pen_tlen[:n].cpu().long()
+        _need(bool(((tl >= 0) & (tl <= W)).all()), "apply_penalties: prompt-tail length out of range")
+        _need(bool((pen_last[:n].cpu().long() >= 0).all()), "apply_penalties: negative window length")
+        _need(bool((nout[:n].cpu().long() >= 0).all()), "apply_penalties: negative output count")
+    if logits.is_cuda:
+        _k().apply_penalties(logits, row_of_slot, done_state, state, nout, out_tokens, pen_par, pen_last, pen_tail,
+                             pen_tlen)
+    else:
+        ref.apply_penalties(logits, row_of_slot, done_state, state, nout, out_tokens, pen_par, pen_last, pen_tail,
+                            pen_tlen)
 
 
 def attention_tiles(q_lens: list[int], hq: int, hkv: int, nqt: int) -> list[tuple[int, int]]:

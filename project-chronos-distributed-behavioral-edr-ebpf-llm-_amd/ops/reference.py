@@ -281,3 +281,30 @@ def token_logprobs_commit(logits, row_of_slot, nout, out_tokens, lp_want, lp_mar
         out_lp[slot, i, 0] = logits[row, int(out_tokens[slot, i])].float() - lse
         out_lp[slot, i, 1:] = lp_top_val[slot] - lse
         out_lp_ids[slot, i] = lp_top_ids[slot]
+
+
+def apply_penalties(logits, row_of_slot, done_state: int, state, nout, out_tokens, pen_par, pen_last, pen_tail,
+                    pen_tlen) -> None:
+    """fp32 reference of csrc/kernels/penalties.hip (host loop over the slots, torch.unique for the counts); the
+    penalised values are rounded to the logits dtype at the end, as the kernel's store does."""
+    W, max_out, width = pen_tail.shape[1], out_tokens.shape[1], logits.shape[1]
+    for slot in range(state.numel()):
+        s = int(state[slot])
+        if s < 0 or s == done_state:
+            continue
+        row = int(row_of_slot[slot]) if row_of_slot is not None else slot
+        L = min(int(pen_last[slot]), W)
+        rp, fq, pr = (pen_par[slot, i] for i in range(3))  # f32 scalars: the arithmetic below stays in fp32
+        if row < 0 or L <= 0 or (float(rp) == 1.0 and float(fq) == 0.0 and float(pr) == 0.0):
+            continue
+        tl = min(max(int(pen_tlen[slot]), 0), W)
+        no = min(max(int(nout[slot]), 0), max_out)
+        hist = torch.cat([pen_tail[slot, :tl].long(), out_tokens[slot, :no].long()])[-L:]
+        hist = hist[(hist >= 0) & (hist < width)]
+        if hist.numel() == 0:
+            continue
+        ids, cnt = torch.unique(hist, return_counts=True)
+        x = logits[row, ids].float()
+        x = torch.where(x <= 0, x * rp, x / rp)
+        x = x - (cnt.float() * fq + pr)
+        logits[row, ids] = x.to(logits.dtype)

@@ -59,7 +59,8 @@ def _worker(rank: int, cfg_dict: dict, req_q, res_q, device: str, fail_start: bo
             res_q.put(("done", rid, dict(text=r.text, error=r.error, prompt_ids=list(r.prompt_ids),
                                          out_ids=list(r.out_ids), done_reason=r.done_reason, t_submit=r.t_submit,
                                          t_admit=r.t_admit, t_first=r.t_first, t_done=r.t_done, rank=rank,
-                                         logprobs=r.logprobs, out_logprobs=list(r.out_logprobs))))
+                                         logprobs=r.logprobs, out_logprobs=list(r.out_logprobs),
+                                         penalty=r.penalty)))
         return cb
 
     def tokens(rid):
@@ -91,7 +92,9 @@ def _worker(rank: int, cfg_dict: dict, req_q, res_q, device: str, fail_start: bo
             live[rid] = eng.submit(ids, fmt=p.format, num_predict=p.num_predict, temperature=p.temperature,
                                    seed=p.seed, top_k=p.top_k, top_p=p.top_p, callback=finish(rid),
                                    meta={"rid": rid, **({"on_tokens": tokens(rid)} if stream else {})},
-                                   max_len=p.num_ctx or None, logprobs=p.logprobs)
+                                   max_len=p.num_ctx or None, logprobs=p.logprobs, repeat_penalty=p.repeat_penalty,
+                                   frequency_penalty=p.frequency_penalty, presence_penalty=p.presence_penalty,
+                                   repeat_last_n=p.repeat_last_n)
             try:
                 item = req_q.get_nowait()
             except queue.Empty:
