@@ -47,6 +47,8 @@ void launch_token_logprobs_commit(const void*, bool, int64_t, int, const int32_t
 void launch_apply_penalties(void*, bool, int64_t, int, const int32_t*, int, int, const int32_t*, const int32_t*,
                             const int32_t*, int, const float*, const int32_t*, const int32_t*, const int32_t*, int,
                             hipStream_t);
+void launch_truncate_logits(void*, bool, int64_t, const int32_t*, int, int, const int16_t*, const int16_t*, int,
+                            const int32_t*, const int32_t*, const float*, const float*, const float*, hipStream_t);
 void launch_gemv(const uint16_t*, int, int, const uint16_t*, int, uint16_t*, bool, hipStream_t);
 void attn_init();
 void launch_gemm(const uint16_t*, const uint16_t*, uint16_t*, int, int, int, bool, int, hipStream_t);
@@ -505,6 +507,35 @@ void apply_penalties(const Tensor& logits, const c10::optional<Tensor>& row_of_s
                                     (int)logits.size(1), rp, (int)n, (int)done_state, i32(state), i32(nout),
                                     i32(out_tokens), (int)out_tokens.size(1), pen_par.data_ptr<float>(), i32(pen_last),
                                     i32(pen_tail), i32(pen_tlen), (int)W, cur_stream());
+}
+
+// min_p / typical_p (csrc/kernels/truncate.hip): writes -inf, in place and before the sampler, into the legal tokens of
+// each live sampling slot that do not survive.  minp_ln f32 [slots] = ln(min_p) (-inf = off), typical f32 [slots] =
+// typical_p (>= 1 = off).
+void truncate_logits(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, const Tensor& next,
+                     const Tensor& dist, int64_t done_state, const Tensor& state, const Tensor& remaining,
+                     const Tensor& temperature, const Tensor& minp_ln, const Tensor& typical) {
+    chk_gpu(next, "next");
+    CHK(next.scalar_type() == at::kShort && next.dim() == 2, "next must be int16 [S, V]");
+    chk_gpu(dist, "dist");
+    CHK(dist.scalar_type() == at::kShort && dist.numel() == next.size(0), "dist must be int16 [S]");
+    const int64_t vocab = next.size(1);
+    chk_i32(state, "state");
+    const int64_t n = state.numel();
+    const int32_t* rp = chk_lp_rows(logits, row_of_slot, n);
+    CHK(logits.size(1) >= vocab, "logits narrower than the DFA vocabulary");
+    CHK(vocab < (int64_t(1) << 31) - 1024, "vocabulary too wide");  // the kernel strides 1024 tokens in int
+    chk_i32(remaining, "remaining");
+    CHK(remaining.numel() >= n, "remaining: one entry per slot");
+    for (const Tensor* t : {&temperature, &minp_ln, &typical}) {
+        chk_gpu(*t, "temperature / minp_ln / typical");
+        CHK(t->scalar_type() == at::kFloat && t->numel() >= n, "temperature / minp_ln / typical: f32, one per slot");
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+    chronos::launch_truncate_logits(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0), rp, (int)n,
+                                    (int)vocab, next.data_ptr<int16_t>(), dist.data_ptr<int16_t>(), (int)done_state,
+                                    i32(state), i32(remaining), temperature.data_ptr<float>(),
+                                    minp_ln.data_ptr<float>(), typical.data_ptr<float>(), cur_stream());
 }
 
 // y = x @ w.T for M <= 8 rows (decode); swiglu: w = [gate; up] -> y = silu(x@gate.T) * (x@up.T)
@@ -992,6 +1023,8 @@ TORCH_LIBRARY(chronos, m) {
           "Tensor(b!) out_lp_ids) -> ()");
     m.def("apply_penalties(Tensor(a!) logits, Tensor? row_of_slot, int done_state, Tensor state, Tensor nout, "
           "Tensor out_tokens, Tensor pen_par, Tensor pen_last, Tensor pen_tail, Tensor pen_tlen) -> ()");
+    m.def("truncate_logits(Tensor(a!) logits, Tensor? row_of_slot, Tensor next, Tensor dist, int done_state, "
+          "Tensor state, Tensor remaining, Tensor temperature, Tensor minp_ln, Tensor typical) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
@@ -1016,6 +1049,7 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("token_logprobs", &token_logprobs);
     m.impl("token_logprobs_commit", &token_logprobs_commit);
     m.impl("apply_penalties", &apply_penalties);
+    m.impl("truncate_logits", &truncate_logits);
     m.impl("ar_all_reduce", &ar_all_reduce);
     m.impl("ar_all_reduce_norm", &ar_all_reduce_norm);
 }

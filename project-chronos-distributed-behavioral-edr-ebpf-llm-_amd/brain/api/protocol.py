@@ -20,7 +20,21 @@ stream=true NDJSON, timing fields in ns) and /api/chat are served too so any Oll
   ``repeat_last_n`` defaults to 64; 0 switches the penalties off for the request; -1 means as far back as the engine
   keeps; any value above the engine's window (``--penalty-window``, EngineConfig.penalty_window, at most 1024) is
   clamped to that window.  A backend that cannot apply them (server started with ``--penalty-window 0``, the fake
-  backend) answers normally, unpenalised, and names each penalty that is not neutral in ``ignored_options``.
+  backend) answers normally, unpenalised, and names each penalty that is not neutral in ``ignored_options``;
+* ``options.min_p`` (0..1, default 0 = off) and ``options.typical_p`` (above 0 up to 1, default 1 = off) are
+  llama.cpp's truncation samplers, applied on the device inside the decode step (csrc/kernels/truncate.hip) to the
+  raw logits of the *legal set* (below), before temperature, and only when the request samples (temperature > 0:
+  greedy ignores them as it ignores top_k / top_p).  typical_p: with ``p = softmax(logit)`` over the legal tokens and
+  entropy ``H``, tokens are taken by ascending ``|-log p(v) - H|`` until their accumulated probability exceeds
+  ``typical_p``; every token at most as far from ``H`` as the last one taken survives (ties kept: equal logits share
+  their fate, at least one token survives).  min_p, after it: a token survives iff ``p(v) >= min_p * p(best
+  survivor)``, computed as ``logit[v] >= max logit of the survivors + ln(min_p)``; ``min_p: 1`` keeps only the
+  maxima.  The others are masked (-inf) before the sampler.  A grammar-forced token (one legal token) stays forced.
+  Ordering deviation from llama.cpp, whose chain is top_k -> typical_p -> top_p -> min_p: here top_k / top_p stay in
+  the sampler kernel, so the chain is typical_p -> min_p -> top_k -> top_p, each acting on the survivors of the one
+  before.  A backend that cannot apply them (the fake backend) names the non-neutral ones in ``ignored_options``;
+* ``options.mirostat`` (non-zero; ``mirostat_tau`` / ``mirostat_eta`` with it) and ``options.tfs_z`` (other than 1)
+  are not implemented by any backend and are named in ``ignored_options``.
 
 Per-token logprobs (``"logprobs": true`` and optionally ``"top_logprobs": n``, 0 <= n <= 20, both top-level, for
 generate and chat).  The reply gains ``"logprobs": [{"token", "logprob", "bytes", "top_logprobs": [{"token",
@@ -30,7 +44,8 @@ token sampled at output index i (csrc/kernels/logprobs.hip computes them on the 
 * the *legal set* is exactly the sampler's: tokens the request's grammar (``format``) allows in its current state and
   that still let the output close within ``num_predict`` (budget forcing);
 * ``logprob(v) = logit[v] - logsumexp(logit[u] for legal u)``: raw logits, natural log, temperature 1, taken BEFORE
-  any top-k / top-p truncation but AFTER the request's penalties (above): the penalty kernel runs first, the logprob
+  any min_p / typical_p / top-k / top-p truncation but AFTER the request's penalties (above): the penalty kernel
+  runs first, the logprob
   kernels and the sampler both see the penalised row, so a request that asks for both gets the logprobs of the
   distribution its token was actually drawn from — whatever the request's temperature, top_k or top_p.  A token the grammar forces (one
   legal token) has logprob exactly 0.0; without a ``format`` this is the ordinary log-softmax (up to budget forcing
@@ -98,6 +113,10 @@ class GenerateParams:
     presence_penalty: float = 0.0
     repeat_last_n: int = 64
     logprobs: int = -1  # -1 = not asked, 0 = the generated tokens' logprobs, n = with the top n alternatives
+    min_p: float = 0.0      # 0 = off
+    typical_p: float = 1.0  # 1 = off
+    # options that no backend implements and that are not at their neutral value: always in ``ignored_options``
+    unsupported: tuple = ()
 
     @classmethod
     def parse(cls, body: dict, chat: bool = False, default_temperature: float = 0.0) -> "GenerateParams":
@@ -159,6 +178,18 @@ class GenerateParams:
         p.repeat_last_n = last
         if last != 0:
             p.ignored = tuple(k for k, neutral in PENALTY_NEUTRAL if getattr(p, k) != neutral)
+        p.min_p = _number(opts, "min_p", 0.0)
+        if not 0.0 <= p.min_p <= 1.0:
+            raise BadRequest("options.min_p must be a number from 0 to 1")
+        p.typical_p = _number(opts, "typical_p", 1.0)
+        if not 0.0 < p.typical_p <= 1.0:
+            raise BadRequest("options.typical_p must be a number above 0 and at most 1")
+        un = []
+        if (opts.get("mirostat") or 0) != 0:
+            un += [k for k in ("mirostat", "mirostat_tau", "mirostat_eta") if k in opts]
+        if opts.get("tfs_z", 1) not in (1, None):
+            un.append("tfs_z")
+        p.unsupported = tuple(un)
         if chat:
             msgs = body.get("messages")
             if not isinstance(msgs, list) or not msgs:
@@ -206,9 +237,16 @@ def final_fields(req, load_duration: float = 0.0) -> dict:
 
 
 def penalties_ignored(params: GenerateParams, req) -> tuple:
-    """The penalty options of ``params`` to report in ``ignored_options``: its non-neutral ones when the backend did
-    not apply them (a finished engine request carries ``penalty``, a tuple, exactly when its engine did)."""
-    return () if getattr(req, "penalty", None) else params.ignored
+    """The sampling options of ``params`` to report in ``ignored_options``: its non-neutral penalties when the backend
+    did not apply them (a finished engine request carries ``penalty``, a tuple, exactly when its engine did), its
+    non-neutral ``min_p`` / ``typical_p`` when the backend has no truncation kernel (a finished engine request carries
+    ``truncates``; at temperature 0 it is False and nothing is reported: greedy has nothing to truncate), and the
+    options no backend implements (``params.unsupported``)."""
+    pen = () if getattr(req, "penalty", None) else params.ignored
+    tr = ()
+    if getattr(req, "truncates", None) is None:
+        tr = tuple(k for k, neutral in (("min_p", 0.0), ("typical_p", 1.0)) if getattr(params, k) != neutral)
+    return pen + tr + params.unsupported
 
 
 def generate_response(model: str, req, ignored: tuple = ()) -> dict:

@@ -181,6 +181,10 @@ class Request:
     # (repeat_penalty, frequency_penalty, presence_penalty, window length L in 1..penalty_window) of a request the
     # engine penalises; None = neutral parameters, repeat_last_n 0, or an engine with penalty_window 0
     penalty: Optional[tuple] = None
+    # truncation samplers (csrc/kernels/truncate.hip), llama.cpp's: min_p 0 and typical_p 1 are off.  ``truncates``
+    # says whether the engine applies them to this request (never at temperature 0: greedy ignores truncation)
+    min_p: float = 0.0
+    typical_p: float = 1.0
     # runtime
     pending_text: Optional[tuple] = None  # (prompt, system, raw) until tokenized at admission
     slot: int = -1
@@ -204,6 +208,11 @@ class Request:
     resume_lp: list = field(default_factory=list)  # out_logprobs entries of resume_out
     orig_plen: int = -1
     preemptions: int = 0
+
+    @property
+    def truncates(self) -> bool:
+        """Does the engine apply a min_p / typical_p to this request?"""
+        return self.min_p > 0.0 or self.typical_p < 1.0
 
     @property
     def kv_cap(self) -> int:
@@ -330,6 +339,9 @@ class Engine:
         self._starting: tuple | list = ()  # prompts whose first token the sampler launch being queued samples
         # penalties: allocated by _pen_alloc when the first penalised request starts (None = never asked)
         self.s_penpar = self.s_penlast = self.s_pentail = self.s_pentlen = None
+        # min_p / typical_p: ln(min_p) and typical_p per slot, allocated by _tr_alloc when the first request that
+        # truncates starts (None = never asked)
+        self.s_minpln = self.s_typ = None
         self.ar = torch.arange(S + 1, **i32)
         self.ar64 = torch.arange(S, dtype=torch.int64, device=dev)
         # ---- scheduling state ----
@@ -340,7 +352,8 @@ class Engine:
         self.free_slots = list(range(S - 1, -1, -1))
         self._rid = itertools.count()
         # (rows, kv splits, steps) -> graph; the variant with the logprob kernels: (rows, kv splits, steps, 1); the
-        # variants with the penalty kernel: (rows, kv splits, steps, 0 or 1 for the logprob kernels, "pen") — _gkey
+        # variants with the penalty kernel: (rows, kv splits, steps, 0 or 1 for the logprob kernels, "pen"); with the
+        # truncation kernel: (rows, kv splits, steps, 0 or 1 logprobs, 0 or 1 penalties, "tr") — _gkey
         self._graphs: dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
         self.stats = collections.Counter()
@@ -377,12 +390,16 @@ class Engine:
                seed: int = 0, raw: bool = False, system: str | None = None,
                callback: Callable[[Request], None] | None = None, meta: dict | None = None, top_k: int = 0,
                top_p: float = 1.0, max_len: int | None = None, logprobs: int = -1, repeat_penalty: float = 1.0,
-               frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64) -> Request:
+               frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64,
+               min_p: float = 0.0, typical_p: float = 1.0) -> Request:
         """Queue a request.  A text prompt is tokenized (chat template) lazily at admission, a prefill chunk's worth
         at a time, so host tokenization of a large wave overlaps the GPU prefill of the previous chunk.
 
         Penalties (llama.cpp's): neutral by default; ``repeat_last_n`` 0 = off, -1 = the engine's whole window, above
-        ``penalty_window`` = clamped to it.  An engine with ``penalty_window`` 0 accepts and does not apply them."""
+        ``penalty_window`` = clamped to it.  An engine with ``penalty_window`` 0 accepts and does not apply them.
+
+        ``min_p`` (0 = off) and ``typical_p`` (1 = off) are llama.cpp's truncation samplers, applied on the device
+        before top-k / top-p (csrc/kernels/truncate.hip); a request at temperature 0 is greedy: they stay neutral."""
         n = num_predict if num_predict and num_predict > 0 else self.cfg.default_num_predict
         req = Request(next(self._rid), prompt if isinstance(prompt, list) else [], fmt, min(n, self.cfg.max_out),
                       float(temperature or 0.0), int(seed or 0), callback, meta or {})
@@ -395,6 +412,10 @@ class Engine:
         if self.cfg.penalty_window > 0 and last != 0 and (rp != 1.0 or fq != 0.0 or pr != 0.0):
             W = self.cfg.penalty_window
             req.penalty = (rp, fq, pr, W if last < 0 else min(last, W))
+        if req.temperature > 0:
+            req.min_p = min(max(float(min_p or 0.0), 0.0), 1.0)
+            tp = 1.0 if typical_p is None else float(typical_p)
+            req.typical_p = tp if 0.0 < tp < 1.0 else 1.0
         if max_len:  # the request's own context window (Ollama options.num_ctx), within the engine's
             req.meta["max_len"] = min(int(max_len), self.cfg.max_model_len)
         req.t_submit = time.perf_counter()
@@ -888,6 +909,26 @@ class Engine:
                 self.s_pentail[sl] = dv(torch.tensor([t + [-1] * (W - len(t)) for t in tails], dtype=torch.int32))
                 self.s_pentlen[sl] = dv(torch.tensor([len(t) for t in tails], dtype=torch.int32))
 
+        if self.s_minpln is None and any(r.truncates for r in done_reqs):
+            self._tr_alloc()
+        if self.s_minpln is not None:  # every starting slot: a reused one may hold a truncating request's values
+            self.s_minpln[sl] = dv(torch.tensor([math.log(r.min_p) if r.min_p > 0 else -math.inf for r in done_reqs],
+                                                dtype=torch.float32))
+            self.s_typ[sl] = dv(torch.tensor([r.typical_p for r in done_reqs], dtype=torch.float32))
+
+    # ---- min_p / typical_p ------------------------------------------------------------------------------------------
+    def _tr_alloc(self) -> None:
+        S, dev = self.cfg.max_slots, self.device
+        self.s_minpln = torch.full((S,), -math.inf, dtype=torch.float32, device=dev)
+        self.s_typ = torch.ones(S, dtype=torch.float32, device=dev)
+
+    def _tr_on(self) -> bool:
+        """Does a request with a non-neutral min_p / typical_p take part in the sampler launch about to be queued
+        (running, or in ``_starting``)?  False at once on an engine that was never asked."""
+        if self.s_minpln is None:
+            return False
+        return any(r.truncates for r in self.running.values()) or any(r.truncates for r in self._starting)
+
     # ---- penalties --------------------------------------------------------------------------------------------------
     @property
     def can_penalise(self) -> bool:
@@ -909,9 +950,11 @@ class Engine:
         return any(r.penalty for r in self.running.values()) or any(r.penalty for r in self._starting)
 
     @staticmethod
-    def _gkey(n: int, ns: int, k: int, lp: bool, pen: bool) -> tuple:
+    def _gkey(n: int, ns: int, k: int, lp: bool, pen: bool, tr: bool = False) -> tuple:
         """Decode-graph key: (n, ns, k), with the logprob kernels (n, ns, k, 1), with the penalty kernel
-        (n, ns, k, 0 or 1, "pen")."""
+        (n, ns, k, 0 or 1, "pen"), with the truncation kernel (n, ns, k, 0 or 1, 0 or 1, "tr")."""
+        if tr:
+            return (n, ns, k, int(lp), int(pen), "tr")
         if pen:
             return (n, ns, k, int(lp), "pen")
         return (n, ns, k, 1) if lp else (n, ns, k)
@@ -960,7 +1003,9 @@ class Engine:
     def _sample(self, logits, jump) -> None:
         """One sampler launch over the slots of ``s_row``; bracketed by the logprob kernels when a request that wants
         them is running or starting in this launch (_lp_on), preceded by the penalty kernel when a penalised one is
-        (_pen_on): the logprob kernels and the sampler both see the penalised rows."""
+        (_pen_on): the logprob kernels and the sampler both see the penalised rows.  The min_p / typical_p kernel
+        (_tr_on) runs last before the sampler, after the logprob pre-kernel: logprobs are taken before any truncation,
+        and the commit kernel reads only the chosen token's logit — a survivor's, which truncation never rewrites."""
         if self._pen_on():
             ops.apply_penalties(logits, self.s_row, DONE, self.s_state, self.s_nout, self.s_out, self.s_penpar,
                                 self.s_penlast, self.s_pentail, self.s_pentlen)
@@ -969,6 +1014,10 @@ class Engine:
         if lp:
             ops.token_logprobs(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
                                self.s_nout, self.s_lpwant, self.s_lpmark, self.s_lplse, self.s_lptid, self.s_lptval)
+        if self._tr_on():
+            ops.truncate_logits(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
+                                self.s_temp, self.s_minpln, self.s_typ)
+            self.stats["truncate_launches"] += 1
         ops.constrained_sample(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
                                self.s_temp, self.s_seed, self.s_ids, self.s_pos, self.s_ctx, self.s_nout, self.s_out,
                                self.s_topk, self.s_topp, jump)
@@ -1085,10 +1134,11 @@ class Engine:
     def _decode_rows(self) -> int:
         return _bucket(max(self.running) + 1) if self.running else 0
 
-    def _decode_once(self, n: int, nsplit: int, lp: bool = False, pen: bool = False) -> None:
+    def _decode_once(self, n: int, nsplit: int, lp: bool = False, pen: bool = False, tr: bool = False) -> None:
         """One decode step of the first n slots.  ``lp``: a running request wants logprobs, so the sampler launch is
         bracketed by the logprob kernels (and never parks: _jump_flags).  ``pen``: a running request is penalised, so
-        the penalty kernel rewrites the logits first."""
+        the penalty kernel rewrites the logits first.  ``tr``: a running request has a min_p / typical_p, so the
+        truncation kernel runs right before the sampler."""
         sb = StepBatch(self.s_ids[:n], self.s_pos[:n], self.ar[:n], self.s_bt[:n], self.ar[:n + 1], self.s_ctx[:n],
                        self.ar64[:n], None, n, 1, nsplit, casc=self._casc)
         logits = self.model.forward(sb, self.kv)
@@ -1099,6 +1149,9 @@ class Engine:
             ops.token_logprobs(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
                                self.s_nout[:n], self.s_lpwant[:n], self.s_lpmark[:n], self.s_lplse[:n],
                                self.s_lptid[:n], self.s_lptval[:n])
+        if tr:
+            ops.truncate_logits(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
+                                self.s_temp[:n], self.s_minpln[:n], self.s_typ[:n])
         ops.constrained_sample(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
                                self.s_temp[:n], self.s_seed[:n], self.s_ids[:n], self.s_pos[:n], self.s_ctx[:n],
                                self.s_nout[:n], self.s_out[:n], self.s_topk[:n], self.s_topp[:n],
@@ -1154,19 +1207,21 @@ class Engine:
         self._update_casc()
         n = min(self._decode_rows(), self.cfg.max_slots)
         ns = self._nsplit(n, self._ctx_class())
-        lp, pen = self._lp_on(), self._pen_on()
+        lp, pen, tr = self._lp_on(), self._pen_on(), self._tr_on()
         if self.device.type == "cuda" and self.cfg.use_graphs:
-            g = self._graphs.get(self._gkey(n, ns, k, lp, pen))
+            g = self._graphs.get(self._gkey(n, ns, k, lp, pen, tr))
             if g is None:
-                g = self._capture(n, ns, k, lp, pen)
+                g = self._capture(n, ns, k, lp, pen, tr)
             g.replay()
         else:
             self._gate(n)
             try:
                 for _ in range(k):
-                    self._decode_once(n, ns, lp, pen)
+                    self._decode_once(n, ns, lp, pen, tr)
             finally:
                 self._gate(0)
+        if tr:
+            self.stats["truncate_launches"] += k
         if lp:
             self.stats["logprob_launches"] += k
         if pen:
@@ -1209,7 +1264,8 @@ class Engine:
         if self.device.type == "cuda" and self.cfg.decode_gate:
             ops.set_decode_gate(self.s_state, n if 0 < n <= 8 else 0)
 
-    def _capture(self, n: int, ns: int, k: int, lp: bool = False, pen: bool = False) -> "torch.cuda.CUDAGraph":
+    def _capture(self, n: int, ns: int, k: int, lp: bool = False, pen: bool = False,
+                 tr: bool = False) -> "torch.cuda.CUDAGraph":
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
@@ -1218,10 +1274,10 @@ class Engine:
         try:
             with torch.cuda.graph(g, pool=self._graph_pool):
                 for _ in range(k):
-                    self._decode_once(n, ns, lp, pen)
+                    self._decode_once(n, ns, lp, pen, tr)
         finally:
             self._gate(0)
-        self._graphs[self._gkey(n, ns, k, lp, pen)] = g
+        self._graphs[self._gkey(n, ns, k, lp, pen, tr)] = g
         self.stats["graphs_captured"] += 1
         return g
 
@@ -1419,6 +1475,8 @@ class Engine:
             lp += (self.s_penpar, self.s_penlast)
             if self._pen_on():
                 lp += (self.s_pentail, self.s_pentlen)
+        if self.s_minpln is not None:  # and the min_p / typical_p parameters
+            lp += (self.s_minpln, self.s_typ)
         for t in (self.s_ids, self.s_pos, self.s_ctx, self.s_state, self.s_rem, self.s_nout, self.s_seed, self.s_temp,
                   self.s_topk, self.s_topp, self.s_out, self.s_bt, *lp):
             t[di] = t[si]

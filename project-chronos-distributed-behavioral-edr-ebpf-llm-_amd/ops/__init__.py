@@ -4,7 +4,7 @@ There is no silent fallback on a GPU: a CUDA/HIP tensor always goes to ``torch.o
 extension (``_C*.so``, built by :mod:`chronos.native`) cannot be built or loaded the op raises.  CPU tensors (tests,
 the gloo-backed distributed tests, the CPU plumbing config) take :mod:`.reference`.
 
-Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties}.hip.
+Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties,truncate}.hip.
 """
 from __future__ import annotations
 
@@ -382,6 +382,45 @@ def apply_penalties(logits, row_of_slot, done_state: int, state, nout, out_token
     else:
         ref.apply_penalties(logits, row_of_slot, done_state, state, nout, out_tokens, pen_par, pen_last, pen_tail,
                             pen_tlen)
+
+
+def truncate_logits(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, temperature, minp_ln,
+                    typical) -> None:
+    """Launched AFTER ``apply_penalties`` / ``token_logprobs`` and BEFORE ``constrained_sample`` on the same logits:
+    llama.cpp's typical_p, then min_p, in place.  For every live slot (the sampler's test, row addressing and legal
+    set) with ``temperature > 0`` whose ``minp_ln[slot]`` = ln(min_p) is above -inf or whose ``typical[slot]`` is
+    below 1, the legal tokens that do not survive get -inf in the row's dtype: typical_p keeps the tokens whose
+    ``|-logp - H|`` is at most that of the first token, by ascending distance, at which the accumulated probability
+    exceeds ``typical``; min_p then keeps ``x >= max(x of the survivors) + minp_ln``.  No other logit is touched, and
+    a row with at most one legal token not at all (csrc/kernels/truncate.hip)."""
+    if _checking(logits):
+        st = state.cpu().long()
+        S, n = next_tab.shape[0], state.shape[0]
+        _need(bool(((st >= -1 - S) & (st < S)).all()), "truncate_logits: grammar state out of range")
+        _need(next_tab.shape[1] <= logits.shape[-1], "truncate_logits: grammar table wider than the logits")
+        _need(dist.shape[0] == S, "truncate_logits: dist must have one entry per grammar state")
+        if row_of_slot is not None:
+            rs = row_of_slot.cpu().long()
+            _need(row_of_slot.shape[0] >= n, "truncate_logits: row_of_slot shorter than the slots")
+            _need(bool(((rs >= -1) & (rs < logits.shape[0])).all()), "truncate_logits: logits row out of range")
+        else:
+            _need(n <= logits.shape[0], "truncate_logits: more slots than logits rows")
+        _need(min(remaining.shape[0], temperature.shape[0], minp_ln.shape[0], typical.shape[0]) >= n,
+              "truncate_logits: per-slot shapes")
+        _need(bool((minp_ln[:n].cpu() <= 0).all()), "truncate_logits: ln(min_p) above 0")
+        _need(bool((typical[:n].cpu() > 0).all()), "truncate_logits: typical_p must be positive")
+    if logits.is_cuda:
+        _k().truncate_logits(logits, row_of_slot, next_tab, dist, done_state, state, remaining, temperature, minp_ln,
+                             typical)
+    else:
+        ref.truncate_logits(logits, row_of_slot, next_tab, dist, done_state, state, remaining, temperature, minp_ln,
+                            typical)
+
+
+def truncate_survivors(x, legal, minp_ln: float, typical: float, dtype=torch.float32):
+    """The reference survivor mask of one row (:func:`.reference.truncate_survivors`): what ``truncate_logits`` keeps
+    of the ``legal`` tokens of logits row ``x``."""
+    return ref.truncate_survivors(x, legal, minp_ln, typical, dtype)
 
 
 def attention_tiles(q_lens: list[int], hq: int, hkv: int, nqt: int) -> list[tuple[int, int]]:

@@ -308,3 +308,59 @@ def apply_penalties(logits, row_of_slot, done_state: int, state, nout, out_token
         x = torch.where(x <= 0, x * rp, x / rp)
         x = x - (cnt.float() * fq + pr)
         logits[row, ids] = x.to(logits.dtype)
+
+
+def truncate_survivors(x: torch.Tensor, legal: torch.Tensor, minp_ln: float, typical: float,
+                       dtype=torch.float32) -> torch.Tensor:
+    """Survivor mask of one logits row under typical_p then min_p (llama.cpp's semantics on raw logits, over the
+    legal tokens only; csrc/kernels/truncate.hip).  ``x`` [V] logits, ``legal`` [V] bool, ``minp_ln`` = ln(min_p)
+    (-inf = off), ``typical`` = typical_p (>= 1 = off).  Returns a bool [V] mask, a subset of ``legal``; with at most
+    one legal token, or no legal logit above -inf, it is ``legal`` itself.  ``dtype``: the arithmetic's precision
+    (float64 gives the tests their yardstick); the min_p comparison is always the fp32 ``x >= m' + ln p``."""
+    keep = legal.clone()
+    idx = legal.nonzero().flatten()
+    if idx.numel() < 2:
+        return keep
+    xf = x.float()[idx]
+    if float(xf.max()) == float("-inf"):
+        return keep
+    alive = torch.ones_like(xf, dtype=torch.bool)
+    if typical < 1.0:
+        xl = xf.to(dtype)
+        dx = xl - xl.max()
+        e = torch.exp(dx)
+        logp = dx - torch.log(e.sum())
+        p = e / e.sum()
+        H = -(torch.where(p > 0, p * logp, torch.zeros_like(p))).sum()
+        d = (-logp - H).abs()
+        order = torch.sort(d, stable=True).indices
+        cum = torch.cumsum(p[order], 0)
+        over = (cum > typical).nonzero().flatten()
+        dstar = d[order[int(over[0])]] if over.numel() else d[order[-1]]
+        alive = d <= dstar
+    if minp_ln > float("-inf"):
+        m2 = xf[alive].max()
+        alive = alive & (xf >= m2 + torch.tensor(minp_ln, dtype=torch.float32))
+    keep[idx] = alive
+    return keep
+
+
+def truncate_logits(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, temperature, minp_ln,
+                    typical) -> None:
+    """fp32 reference of csrc/kernels/truncate.hip (host loop over the slots): -inf, in place, into the legal tokens
+    of each live sampling slot that typical_p and then min_p remove."""
+    V = next_tab.shape[1]
+    for slot in range(state.numel()):
+        s = int(state[slot])
+        if s < 0 or s == done_state:
+            continue
+        row = int(row_of_slot[slot]) if row_of_slot is not None else slot
+        lnp, tp = float(minp_ln[slot]), float(typical[slot])
+        if row < 0 or not float(temperature[slot]) > 0.0 or (lnp == float("-inf") and not tp < 1.0):
+            continue
+        nx = next_tab[s].long()
+        legal = (nx >= 0) & (dist[nx.clamp(min=0)].long() <= int(remaining[slot]) - 1)
+        keep = truncate_survivors(logits[row, :V], legal, lnp, tp)
+        kill = (legal & ~keep).nonzero().flatten()
+        if kill.numel():
+            logits[row, kill] = float("-inf")

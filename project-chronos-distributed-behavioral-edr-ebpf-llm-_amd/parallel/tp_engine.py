@@ -41,6 +41,7 @@ class _Sub:
     max_len: Optional[int] = None
     logprobs: int = -1  # every rank holds the all-gathered logits, so the ranks' logprobs agree with no extra traffic
     penalties: tuple = (1.0, 0.0, 0.0, 64)  # (repeat, frequency, presence, repeat_last_n): applied by every rank alike
+    truncation: tuple = (0.0, 1.0)  # (min_p, typical_p): likewise
 
 
 @dataclass
@@ -77,7 +78,8 @@ class TPEngine:
     def submit(self, prompt, fmt=None, num_predict: int | None = None, temperature: float = 0.0, seed: int = 0,
                callback: Callable[[Request], None] | None = None, top_k: int = 0, top_p: float = 1.0,
                max_len: int | None = None, logprobs: int = -1, repeat_penalty: float = 1.0,
-               frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64) -> int:
+               frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64,
+               min_p: float = 0.0, typical_p: float = 1.0) -> int:
         assert self.leader, "requests enter through TP rank 0"
         ids = prompt if isinstance(prompt, list) else self.engine.tok.chat_ids(prompt)
         with self._lock:
@@ -86,7 +88,8 @@ class TPEngine:
             if callback is not None:
                 self._callbacks[tag] = callback
         self._inbox.put(_Sub(ids, fmt, num_predict, temperature, seed, tag, top_k, top_p, max_len, logprobs,
-                             (repeat_penalty, frequency_penalty, presence_penalty, repeat_last_n)))
+                             (repeat_penalty, frequency_penalty, presence_penalty, repeat_last_n),
+                             (min_p, typical_p)))
         return tag
 
     def cancel(self, tag: int, reason: str = "cancelled") -> None:
@@ -142,7 +145,8 @@ class TPEngine:
                                    seed=s.seed, callback=cb, meta={"tag": s.tag}, top_k=s.top_k, top_p=s.top_p,
                                    max_len=s.max_len, logprobs=s.logprobs, repeat_penalty=s.penalties[0],
                                    frequency_penalty=s.penalties[1], presence_penalty=s.penalties[2],
-                                   repeat_last_n=s.penalties[3])
+                                   repeat_last_n=s.penalties[3], min_p=s.truncation[0],
+                                   typical_p=s.truncation[1])
             if not r.done_reason:
                 self._reqs[s.tag] = r
         for tag, reason in msg.cancels:
