@@ -147,6 +147,22 @@ inline const float* chk_gemv_w(const Tensor& w, const c10::optional<Tensor>& ws,
     return ws->data_ptr<float>();
 }
 
+// W4A16 decode GEMV weights (we given): packed e2m1 bytes [N, K / 2] with e8m0 block scales [N, K / 32] (OCP MXFP4;
+// csrc/kernels/gemv.hip W4).  Returns the scale-byte pointer, or nullptr when we is absent.
+inline const uint8_t* chk_gemv_w4(const Tensor& w, const c10::optional<Tensor>& ws, const c10::optional<Tensor>& we,
+                                  int64_t K, int64_t M) {
+    if (!we.has_value()) return nullptr;
+    CHK(!ws.has_value(), "ws (fp8 row scales) and we (mxfp4 block scales) are exclusive");
+    chk_gpu(w, "w");
+    chk_gpu(*we, "we");
+    CHK(w.scalar_type() == at::kByte && we->scalar_type() == at::kByte, "mxfp4 GEMV: w and we must be uint8");
+    CHK(K % 1024 == 0 && M >= 1 && M <= 4, "mxfp4 GEMV: K % 1024 == 0, M <= 4 (the fused epilogues: M <= 2)");
+    CHK(w.dim() == 2 && w.size(1) == K / 2, "mxfp4 GEMV: w must be [N, K / 2] (two e2m1 per byte)");
+    CHK(w.size(0) % 16 == 0, "mxfp4 GEMV: N % 16 == 0");
+    CHK(we->dim() == 2 && we->size(0) == w.size(0) && we->size(1) == K / 32, "mxfp4 GEMV: we must be [N, K / 32]");
+    return we->data_ptr<uint8_t>();
+}
+
 // KV caches are bf16 or fp8-e4m3 stored as uint8 (OCP e4m3fn bytes; dequantised with a per-layer scale)
 inline bool chk_kv(const Tensor& k, const Tensor& v) {
     chk_gpu(k, "k_cache");
@@ -539,9 +555,17 @@ void truncate_logits(const Tensor& logits, const c10::optional<Tensor>& row_of_s
 }
 
 // y = x @ w.T for M <= 8 rows (decode); swiglu: w = [gate; up] -> y = silu(x@gate.T) * (x@up.T)
-Tensor gemv(const Tensor& x, const Tensor& w, bool swiglu, const c10::optional<Tensor>& ws) {
+Tensor gemv(const Tensor& x, const Tensor& w, bool swiglu, const c10::optional<Tensor>& ws,
+            const c10::optional<Tensor>& we) {
     chk_bf16(x, "x");
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
+    if (const uint8_t* wex = chk_gemv_w4(w, ws, we, K, M)) {
+        c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+        auto y = at::empty({M, swiglu ? N / 2 : N}, x.options());
+        chronos::launch_gemv_w4(bf(x), (int)M, (int)K, w.data_ptr<uint8_t>(), wex, (int)N, bfm(y), swiglu,
+                                cur_stream());
+        return y;
+    }
     const float* wsc = chk_gemv_w(w, ws, K, M);
     CHK(w.dim() == 2 && w.size(1) == K, "gemv: w must be [N, K]");
     CHK(M >= 1 && M <= 8, "gemv: 1 <= M <= 8");
@@ -574,21 +598,23 @@ void set_decode_gate(const c10::optional<Tensor>& state, int64_t n) {
 // Decode producer (O / down projection at TP=1, M <= 2): resid_out = bf16(bf16(x @ w.T) + resid_in); returns the
 // per-workgroup sums of resid_out^2 [M, P] f32 that the consuming GEMV's norm prologue reduces (chronos_gemv.h).
 Tensor gemv_resid(const Tensor& x, const Tensor& w, const Tensor& resid_in, const Tensor& resid_out,
-                  const c10::optional<Tensor>& ws) {
+                  const c10::optional<Tensor>& ws, const c10::optional<Tensor>& we) {
     chk_bf16(x, "x");
     chk_bf16(resid_in, "resid_in");
     chk_bf16(resid_out, "resid_out");
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
-    const float* wsc = chk_gemv_w(w, ws, K, M);
-    CHK(w.dim() == 2 && w.size(1) == K, "gemv_resid: w must be [N, K]");
+    const uint8_t* wex = chk_gemv_w4(w, ws, we, K, M);
+    const float* wsc = wex ? nullptr : chk_gemv_w(w, ws, K, M);
+    CHK(w.dim() == 2 && (wex || w.size(1) == K), "gemv_resid: w must be [N, K]");
     CHK(M >= 1 && M <= 2 && K % 512 == 0 && N % 16 == 0, "gemv_resid: M <= 2, K % 512, N % 16");
     CHK(resid_in.numel() == M * N && resid_out.numel() == M * N, "gemv_resid: residuals must be [M, N]");
     CHK(resid_in.data_ptr() != resid_out.data_ptr(), "gemv_resid: out of place only");
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     CHK(wsc == nullptr || M <= 2, "gemv_resid: M <= 2");
-    auto part = at::empty({M, chronos::gemv_resid_parts((int)M, (int)N, wsc != nullptr)}, x.options().dtype(at::kFloat));
+    auto part = at::empty({M, chronos::gemv_resid_parts((int)M, (int)N, wex ? 2 : wsc ? 1 : 0)},
+                          x.options().dtype(at::kFloat));
     chronos::launch_gemv_resid(bf(x), (int)M, (int)K, bf(w), (int)N, bf(resid_in), bfm(resid_out),
-                               part.data_ptr<float>(), cur_stream(), wsc);
+                               part.data_ptr<float>(), cur_stream(), wsc, wex);
     return part;
 }
 
@@ -609,17 +635,18 @@ inline chronos::GemvNorm normp_args(const Tensor& s, const Tensor& part, double 
 // fold_norm), the norm's sum of squares taken from a gemv_resid producer's partials (swiglu: gate/up pair ->
 // silu(g) * u).  s: [M, K], M <= 2.
 Tensor gemv_normp(const Tensor& s, const Tensor& part, double eps, const Tensor& w, bool swiglu,
-                  const c10::optional<Tensor>& ws) {
+                  const c10::optional<Tensor>& ws, const c10::optional<Tensor>& we) {
     chk_bf16(s, "s");
     const int64_t K = s.size(-1), M = s.numel() / K, N = w.size(0);
-    const float* wsc = chk_gemv_w(w, ws, K, M);
-    CHK(w.dim() == 2 && w.size(1) == K, "gemv_normp: w must be [N, K]");
+    const uint8_t* wex = chk_gemv_w4(w, ws, we, K, M);
+    const float* wsc = wex ? nullptr : chk_gemv_w(w, ws, K, M);
+    CHK(w.dim() == 2 && (wex || w.size(1) == K), "gemv_normp: w must be [N, K]");
     CHK(M >= 1 && M <= 2 && K % 512 == 0 && N % 16 == 0, "gemv_normp: M <= 2, K % 512, N % 16");
     const chronos::GemvNorm n = normp_args(s, part, eps, M);
     c10::hip::HIPGuardMasqueradingAsCUDA g(s.device());
     auto y = at::empty({M, swiglu ? N / 2 : N}, s.options());
     chronos::launch_gemv_ex(bf(s), (int)M, (int)K, bf(w), (int)N, bfm(y), swiglu, &n, nullptr, false, cur_stream(),
-                            wsc);
+                            wsc, wex);
     return y;
 }
 
@@ -629,7 +656,8 @@ Tensor gemv_normp(const Tensor& s, const Tensor& part, double eps, const Tensor&
 void qkv_rope(const Tensor& x, const c10::optional<Tensor>& part, double eps,
               const Tensor& w, const Tensor& pos, const Tensor& tok_seq, const Tensor& block_table,
               const Tensor& cos_sin, const Tensor& q_out, const Tensor& k_cache, const Tensor& v_cache, int64_t hq,
-              int64_t hkv, double k_scale, double v_scale, const c10::optional<Tensor>& ws) {
+              int64_t hkv, double k_scale, double v_scale, const c10::optional<Tensor>& ws,
+              const c10::optional<Tensor>& we) {
     chk_bf16(x, "x");
     chk_i32(pos, "pos");
     chk_i32(tok_seq, "tok_seq");
@@ -639,9 +667,10 @@ void qkv_rope(const Tensor& x, const c10::optional<Tensor>& part, double eps,
     chk_bf16(q_out, "q_out");
     const bool fp8 = chk_kv(k_cache, v_cache);
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
-    const float* wsc = chk_gemv_w(w, ws, K, M);
+    const uint8_t* wex = chk_gemv_w4(w, ws, we, K, M);
+    const float* wsc = wex ? nullptr : chk_gemv_w(w, ws, K, M);
     CHK(M >= 1 && M <= 2 && K % 512 == 0, "qkv_rope: M <= 2, K % 512 == 0");
-    CHK(w.dim() == 2 && w.size(1) == K && N == (hq + 2 * hkv) * 128, "w must be [(hq+2hkv)*128, K]");
+    CHK(w.dim() == 2 && (wex || w.size(1) == K) && N == (hq + 2 * hkv) * 128, "w must be [(hq+2hkv)*128, K]");
     CHK(pos.numel() >= M && tok_seq.numel() >= M && q_out.numel() >= M * hq * 128, "pos/tok_seq/q_out too small");
     CHK(k_cache.dim() == 4 && k_cache.size(1) == hkv && k_cache.size(3) == 128, "k_cache [NB, hkv, BS, 128]");
     CHK(v_cache.dim() == 4 && v_cache.size(1) == hkv && v_cache.size(2) == 128 && v_cache.size(3) == k_cache.size(2),
@@ -654,7 +683,7 @@ void qkv_rope(const Tensor& x, const c10::optional<Tensor>& part, double eps,
                          bfm(q_out), k_cache.data_ptr(), v_cache.data_ptr(), (int)hq, (int)hkv, (int)k_cache.size(2),
                          (float)(1.0 / k_scale), (float)(1.0 / v_scale)};
     chronos::launch_gemv_ex(bf(x), (int)M, (int)K, bf(w), (int)N, nullptr, false, part.has_value() ? &n : nullptr,
-                            &rp, fp8, cur_stream(), wsc);
+                            &rp, fp8, cur_stream(), wsc, wex);
 }
 
 // y = x @ w.T on MFMA (gemm.hip); swiglu as gemv.  stages = depth of the LDS-DMA ring (2..4)
@@ -981,16 +1010,16 @@ TORCH_LIBRARY(chronos, m) {
           "Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, int hq, int hkv, bool write_q, "
           "float k_scale=1.0, float v_scale=1.0) -> ()");
     m.def("silu_mul(Tensor gate_up) -> Tensor");
-    m.def("gemv(Tensor x, Tensor w, bool swiglu, Tensor? ws=None) -> Tensor");
+    m.def("gemv(Tensor x, Tensor w, bool swiglu, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("gemm(Tensor x, Tensor w, bool swiglu, int stages=3) -> Tensor");
     m.def("gemm_pp(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, bool prio) -> (Tensor, Tensor)");
     m.def("gemm_skinny(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps) "
           "-> (Tensor, Tensor)");
-    m.def("gemv_resid(Tensor x, Tensor w, Tensor resid_in, Tensor(a!) resid_out, Tensor? ws=None) -> Tensor");
-    m.def("gemv_normp(Tensor s, Tensor part, float eps, Tensor w, bool swiglu, Tensor? ws=None) -> Tensor");
+    m.def("gemv_resid(Tensor x, Tensor w, Tensor resid_in, Tensor(a!) resid_out, Tensor? ws=None, Tensor? we=None) -> Tensor");
+    m.def("gemv_normp(Tensor s, Tensor part, float eps, Tensor w, bool swiglu, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("qkv_rope(Tensor x, Tensor? part, float eps, Tensor w, Tensor pos, Tensor tok_seq, "
           "Tensor block_table, Tensor cos_sin, Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, int hq, "
-          "int hkv, float k_scale=1.0, float v_scale=1.0, Tensor? ws=None) -> ()");
+          "int hkv, float k_scale=1.0, float v_scale=1.0, Tensor? ws=None, Tensor? we=None) -> ()");
     m.def("set_decode_gate(Tensor? state, int n) -> ()", &set_decode_gate);
     m.def("attn_init() -> ()", [] { chronos::attn_init(); });
     m.def("quant_rows(Tensor x, Tensor(a!)? resid, Tensor? w, float eps, int mode) -> (Tensor, Tensor)");

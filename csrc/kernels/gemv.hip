@@ -14,6 +14,8 @@
 //     which split K, meet in LDS.
 // One 256-thread workgroup owns R output rows.  Fused SwiGLU epilogue for the gate/up projection (w = [gate; up]):
 // the workgroup streams R gate rows and the matching R up rows and writes silu(g) * u directly.
+#include <type_traits>
+
 #include "chronos_hip.h"
 #include "chronos_gemv.h"
 
@@ -21,6 +23,8 @@ namespace chronos {
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+typedef uint16_t u16x4_t __attribute__((ext_vector_type(4)));
 
 template <typename T>
 __device__ __forceinline__ T ld_nt(const T* p) {
@@ -67,6 +71,23 @@ __device__ __forceinline__ float dot16(const bf16x2_t (&wb)[8], const u16x8& x0,
     return acc;
 }
 
+// W4A16 (OCP MXFP4): an 8-B piece of 16 e2m1 weights (element 2i in the low nibble of byte i) becomes 8 bf16 pairs
+// with v_cvt_scalef32_pk_bf16_fp4, one byte per instruction, the MX block's power-of-two scale (the e8m0 byte moved
+// into an f32 exponent field) applied by the conversion itself — exact: a 1-bit mantissa times a power of two fits
+// bf16 — and meets x in dot16 like the e4m3 pairs.
+__device__ __forceinline__ void q4bf(const u16x4_t& w, uint32_t e, bf16x2_t (&wb)[8]) {
+    const i32x2 wi = __builtin_bit_cast(i32x2, w);
+    const float sc = __builtin_bit_cast(float, e << 23);
+    wb[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[0], sc, 0);
+    wb[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[0], sc, 1);
+    wb[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[0], sc, 2);
+    wb[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[0], sc, 3);
+    wb[4] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[1], sc, 0);
+    wb[5] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[1], sc, 1);
+    wb[6] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[1], sc, 2);
+    wb[7] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi[1], sc, 3);
+}
+
 // Fused decode-step variants (M <= 2 rows: one sensor stream or two), chronos_gemv.h:
 //   * kResid epilogue (O / down projection, TP=1): instead of y, write the new residual s = bf16(bf16(y) + r) and the
 //     workgroup's per-row sum of s^2 — the producer half of the next RMSNorm;
@@ -81,6 +102,8 @@ __device__ __forceinline__ float dot16(const bf16x2_t (&wb)[8], const u16x8& x0,
 //     fp8-e4m3), exactly as rope_kv_write_kernel does from the bf16 qkv output.
 // Together they take a TP=1 decode layer from 9 launches (norm, qkv, rope, attn, combine, o, norm, gate_up, down) to 6.
 enum : int { kPlain = 0, kSwiglu = 1, kRope = 2, kRope8 = 3, kResid = 4 };
+// weight mode: bf16 | e4m3 bytes + per-row scale (W8A16) | packed e2m1 + e8m0 block scales (W4A16, OCP MXFP4)
+enum : int { kW16 = 0, kW8 = 1, kW4 = 2 };
 
 // gemv_kernel: row group g = R output rows.  One group per workgroup (grid = ngroups), or — knob gemv_persist — a
 // smaller grid whose workgroups loop over groups g, g + grid, ...  In the loop the NEXT group's first weight ring is
@@ -91,11 +114,31 @@ enum : int { kPlain = 0, kSwiglu = 1, kRope = 2, kRope8 = 3, kResid = 4 };
 // piece is then 16 elements, a chunk 1024 elements, and x comes as two 16-B pieces per chunk; every fused epilogue is
 // the same, the row sums scaled by their row's weight scale first.  Half the weight bytes of the bf16 kernel, no
 // activation quantisation launch (the W8A8 qgemv path needs one per projection).
-template <int M, int R, int MODE, bool NORMP, bool WQ = false>
+//
+// W4 (W4A16, the mxfp4-weight decode step): W is packed e2m1, K / 2 bytes per row, with one e8m0 scale byte per 32
+// consecutive K elements (nrm.wexp [N, K / 32]).  Geometry: 8-B pieces.  A lane's piece is 16 elements (half an MX
+// block: lanes 2j and 2j + 1 read the same scale byte), a wave-wide load is one contiguous 512 B of a row (four whole
+// 128-B lines) and a chunk is 1024 elements, exactly as WQ — x arrives as the same two 16-B pieces and the four waves
+// split K the same way, so at K = 4096 (QKV, O, gate_up) every wave streams one chunk of every row.  With 16-B
+// pieces (one MX block, one scale byte per lane) a chunk would be 2048 elements and two of the four waves would idle
+// there.  The 32 scale bytes a wave needs per row and chunk are a quarter of a line; at K = 4096 the four waves of the
+// group read the four quarters of the same line.  The block scale goes into the conversion, so totw applies no
+// per-row scale; everything after the dot products (reduction, epilogues, persistent loop, prefetch, gates) is the
+// shared code.  Ring depth: a row's piece is 2 VGPRs + 1 for its scale byte per stage, an x row 8; the ring is 3 deep
+// up to 26 VGPRs per stage and 2 above.  hipcc -Rpass-analysis=kernel-resource-usage, M = 2 with 8 rows (kResid; the
+// M = 2 RoPE groups are the same): depth 2 (40 ring VGPRs per stage), 256 VGPRs + 10 AGPRs, no scratch, one wave
+// per SIMD (depth 3 took 256 + 107; the conversions of a stage's rows are hoisted ahead of the dot products and
+// weigh more than the ring).  M = 1: 8 rows (RoPE, kResid) 213 VGPRs, SwiGLU 4 + 4 rows 214 — two waves per SIMD.
+// Measured on cold weights (scripts/bench_gemv_w4.py, profiles/mxfp4/gemv_table.jsonl) the kernel beats the bf16 GEMV
+// 1.30-1.75x at M = 1 on every 8B projection and loses at M = 2 and 4 (like the bf16 GEMV there, it does not reach the
+// skinny MFMA GEMM), so ops/gemm.py routes M = 1 to it and leaves the larger M instantiations to the tests and the
+// W4_MAX_M switch.
+template <int M, int R, int MODE, bool NORMP, int WM = kW16>
 __global__ void __launch_bounds__(256) gemv_kernel(const uint16_t* __restrict__ x, int mrows, int K,
                                                    const uint16_t* __restrict__ W, uint16_t* __restrict__ y,
                                                    int nout, int half, GemvNorm nrm, GemvRope rp,
                                                    const int32_t* __restrict__ gst, int gn, int ngroups) {
+    constexpr bool WQ = WM == kW8, W4 = WM == kW4;
     constexpr bool SWIGLU = MODE == kSwiglu;
     constexpr bool ROPE = MODE == kRope || MODE == kRope8;
     static_assert(!ROPE || R == 8 || R == 4 || R == 2, "rope epilogue: R/2 rotate-half pairs per workgroup");
@@ -105,8 +148,9 @@ __global__ void __launch_bounds__(256) gemv_kernel(const uint16_t* __restrict__ 
     constexpr int NR = SWIGLU ? 2 * R : R;  // weight rows streamed per group
     constexpr int V = NR * M;               // partial sums per lane
     // register ring depth (VGPR budget): M = 2 with 8 rows at depth 3 took all 256 VGPRs (one wave per SIMD)
-    constexpr int XV = WQ ? 2 : 1;         // 16-B x pieces per lane per chunk
-    constexpr int DEPTH = (NR + XV * M) * 4 < 40 ? 3 : 2;
+    constexpr int XV = WQ || W4 ? 2 : 1;   // 16-B x pieces per lane per chunk
+    constexpr int DEPTH = W4 ? (NR * 3 + XV * M * 4 <= 26 ? 3 : 2) : (NR + XV * M) * 4 < 40 ? 3 : 2;
+    using WP = typename std::conditional<W4, u16x4_t, u16x8>::type;  // a lane's weight piece
     // gn < 0: check the decode gate BEFORE the first weight loads (a closed gate then streams no weights; an open one
     // pays the state read's latency up front).  gn > 0: after them (below).
     if (gn < 0 && gate_closed(gst, -gn)) return;
@@ -114,32 +158,47 @@ __global__ void __launch_bounds__(256) gemv_kernel(const uint16_t* __restrict__ 
     if (g >= ngroups) return;
     __shared__ float red[4][V];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nchunk = WQ ? K >> 10 : K >> 9;  // 1 KiB weight chunks per row (512 bf16 / 1024 e4m3 elements)
+    // weight chunks per row: 1 KiB = 512 bf16 / 1024 e4m3 elements; W4: 512 B = 1024 e2m1 elements
+    const int nchunk = WQ || W4 ? K >> 10 : K >> 9;
     // weight row of the group's r-th streamed row
     auto rowidx = [&](int bid, int r) {
         if constexpr (ROPE) return (bid / RWG) * 128 + (r < RP ? 0 : 64) + RP * (bid % RWG) + (r % RP);
         else return (SWIGLU && r >= R) ? half + bid * R + (r - R) : bid * R + r;
     };
     // row bases are wave-uniform (SGPR pairs); the per-lane part is one 32-bit offset (lane + 64 * chunk) * 16 B
-    const u16x8* wrow[NR];
+    const WP* wrow[NR];
+    const uint8_t* erow[W4 ? NR : 1];  // W4: the row's e8m0 scale bytes
     auto set_rows = [&](int bid) {
 #pragma unroll
-        for (int r = 0; r < NR; ++r)
-            wrow[r] = reinterpret_cast<const u16x8*>(reinterpret_cast<const uint8_t*>(W) +
-                                                     (int64_t)rowidx(bid, r) * K * (WQ ? 1 : 2));
+        for (int r = 0; r < NR; ++r) {
+            if constexpr (W4) {
+                wrow[r] = reinterpret_cast<const WP*>(reinterpret_cast<const uint8_t*>(W) +
+                                                      (int64_t)rowidx(bid, r) * (K >> 1));
+                erow[r] = nrm.wexp + (int64_t)rowidx(bid, r) * (K >> 5);
+            } else {
+                wrow[r] = reinterpret_cast<const WP*>(reinterpret_cast<const uint8_t*>(W) +
+                                                      (int64_t)rowidx(bid, r) * K * (WQ ? 1 : 2));
+            }
+        }
     };
     const u16x8* xr = reinterpret_cast<const u16x8*>(x);
     const int xstride = K >> 3;
-    u16x8 wr[DEPTH][NR], xv[DEPTH][M][XV];
+    WP wr[DEPTH][NR];
+    u16x8 xv[DEPTH][M][XV];
+    uint32_t se[DEPTH][W4 ? NR : 1];
     auto load = [&](int c, int d) {
         const int off = c * 64 + lane;
 #pragma unroll
         for (int r = 0; r < NR; ++r) wr[d][r] = ld_nt(wrow[r] + off);
+        if constexpr (W4) {  // the scale byte of the MX block this lane's 16 elements lie in
+#pragma unroll
+            for (int r = 0; r < NR; ++r) se[d][r] = erow[r][c * 32 + (lane >> 1)];
+        }
 #pragma unroll
         for (int m = 0; m < M; ++m)
 #pragma unroll
             for (int v = 0; v < XV; ++v)
-                xv[d][m][v] = m < mrows ? xr[m * xstride + (WQ ? c * 128 + 2 * lane + v : off)]
+                xv[d][m][v] = m < mrows ? xr[m * xstride + (WQ || W4 ? c * 128 + 2 * lane + v : off)]
                                         : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
     };
     // wave w takes chunks w, w+4, w+8, ... of every row
@@ -199,9 +258,10 @@ __global__ void __launch_bounds__(256) gemv_kernel(const uint16_t* __restrict__ 
                 if (c < nchunk) {
 #pragma unroll
                     for (int r = 0; r < NR; ++r) {
-                        if constexpr (WQ) {
+                        if constexpr (WQ || W4) {
                             bf16x2_t wb[8];
-                            q2bf(wr[d][r], wb);
+                            if constexpr (W4) q4bf(wr[d][r], se[d][r], wb);
+                            else q2bf(wr[d][r], wb);
 #pragma unroll
                             for (int m = 0; m < M; ++m)
                                 acc[r * M + m] = dot16(wb, xv[d][m][0], xv[d][m][1], acc[r * M + m]);
@@ -215,7 +275,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const uint16_t* __restrict__ 
             }
         }
         const int bid = g, n0 = g * R;
-        // the row sum of output i (= r * M + m) with its row's fp8 weight scale
+        // the row sum of output i (= r * M + m) with its row's fp8 weight scale (W4: the block scales are in the sums)
         auto totw = [&](int i) {
             float v = tot(i);
             if constexpr (WQ) v *= nrm.wscale[rowidx(bid, i / M)];
@@ -329,8 +389,9 @@ constexpr int rows_swiglu() { return M <= 2 ? 4 : 2; }
 // M = 1) still covers N / R, else 8.  The partials buffer is sized by gemv_resid_parts with the same choice.
 // fp8 weights (WQ): twice the rows per group — a group then streams the same bytes as the bf16 kernel's (at K = 4096
 // a wave holds a single 1 KiB chunk per row, so the per-group reduction / epilogue is amortised over 2x the rows)
-static int resid_rows(int N, bool wq = false) {
-    const int r = wq ? knob("gemv_q_r_resid", 8) : knob("gemv_r_resid", 4);
+// mxfp4 weights (W4): the WQ rows (a group streams half the bf16 kernel's bytes; knobs gemv_w4_r_*)
+static int resid_rows(int N, int wm = kW16) {
+    const int r = wm == kW8 ? knob("gemv_q_r_resid", 8) : wm == kW4 ? knob("gemv_w4_r_resid", 8) : knob("gemv_r_resid", 4);
     if (r == 2 && N / 2 <= 2048 && N % 2 == 0) return 2;
     return (r == 4 && N / 4 <= 2048 && N % 4 == 0) ? 4 : 8;
 }
@@ -347,9 +408,11 @@ static int rows_knob(const char* name, int dflt) {
     return (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : dflt;
 }
 
-template <int M, bool WQ = false>
+template <int M, int WM = kW16>
 static void launch_m(const uint16_t* x, int mrows, int K, const uint16_t* W, int N, uint16_t* y, int mode,
-                     const GemvNorm* nrm, const GemvRope* rp, hipStream_t st, const float* wscale = nullptr) {
+                     const GemvNorm* nrm, const GemvRope* rp, hipStream_t st, const float* wscale = nullptr,
+                     const uint8_t* wexp = nullptr) {
+    constexpr bool WQ = WM != kW16;  // quantised weights (e4m3 or mxfp4): the same rows per group
     // WQ: twice the plain rows (O / down / QKV groups then stream the bf16 kernel's bytes); SwiGLU keeps its rows
     // (gate_up at M = 1: 27.4 us with 4 + 4 rows, 35.9 with 8 + 8; profiles/r5/w8a16_*)
     constexpr int R1 = rows_plain<M>() * (WQ ? 2 : 1), R2 = rows_swiglu<M>();
@@ -358,6 +421,7 @@ static void launch_m(const uint16_t* x, int mrows, int K, const uint16_t* W, int
     const GemvRope rz{};
     GemvNorm na = nrm ? *nrm : nz;
     na.wscale = wscale;
+    if (WM == kW4) na.wexp = wexp;
     const GemvRope ra = rp ? *rp : rz;
     const bool np = nrm && nrm->part;  // consumer of a kResid producer
     const int32_t* gst = g_gate_n > 0 && g_gate_n <= kGateMax ? g_gate_state : nullptr;
@@ -373,16 +437,16 @@ static void launch_m(const uint16_t* x, int mrows, int K, const uint16_t* W, int
     const int persist = knob("gemv_persist", -1);
 #define GV(MODE_, NP_, RR, GRID, NOUT, HALF)                                                                     \
     do {                                                                                                         \
-        const int fit_ = resident_workgroups(gemv_kernel<M, RR, MODE_, NP_, WQ>, 256);                          \
+        const int fit_ = resident_workgroups(gemv_kernel<M, RR, MODE_, NP_, WM>, 256);                          \
         const int cap_ = persist == 0 ? (GRID) : persist > 0 && persist < fit_ ? persist : fit_;                 \
-        hipLaunchKernelGGL((gemv_kernel<M, RR, MODE_, NP_, WQ>), dim3(cap_ < (GRID) ? cap_ : (GRID)), dim3(256), \
+        hipLaunchKernelGGL((gemv_kernel<M, RR, MODE_, NP_, WM>), dim3(cap_ < (GRID) ? cap_ : (GRID)), dim3(256), \
                            0,                                                                                    \
                            st, x, mrows, K, W, y, NOUT, HALF, na, ra, gst, gn, (GRID));                          \
     } while (0)
     if (mode == kSwiglu) {
         const int F = N / 2;
         if constexpr (M == 1) {
-            const int r = rows_knob(WQ ? "gemv_q_r_swiglu" : "gemv_r_swiglu", R2);
+            const int r = rows_knob(WM == kW8 ? "gemv_q_r_swiglu" : WM == kW4 ? "gemv_w4_r_swiglu" : "gemv_r_swiglu", R2);
             if (r == 1) {
                 if (np) GV(kSwiglu, true, 1, F, F, F); else GV(kSwiglu, false, 1, F, F, F);
                 return;
@@ -400,7 +464,7 @@ static void launch_m(const uint16_t* x, int mrows, int K, const uint16_t* W, int
         else GV(kSwiglu, false, R2, F / R2, F, F);
     } else if (mode == kPlain) {
         if constexpr (M == 1) {
-            const int r = rows_knob(WQ ? "gemv_q_r_plain" : "gemv_r_plain", R1);
+            const int r = rows_knob(WM == kW8 ? "gemv_q_r_plain" : WM == kW4 ? "gemv_w4_r_plain" : "gemv_r_plain", R1);
             if (r == 2 && N % 2 == 0) {
                 if (np) GV(kPlain, true, 2, N / 2, N, 0); else GV(kPlain, false, 2, N / 2, N, 0);
                 return;
@@ -418,7 +482,7 @@ static void launch_m(const uint16_t* x, int mrows, int K, const uint16_t* W, int
         else GV(kPlain, false, R1, N / R1, N, 0);
     } else if constexpr (M <= 2) {
         if (mode == kResid) {
-            const int r = M == 1 ? resid_rows(N, WQ) : RP;
+            const int r = M == 1 ? resid_rows(N, WM) : RP;
             if constexpr (M == 1) {
                 if (r == 4) {
                     GV(kResid, false, 4, N / 4, N, 0);
@@ -431,7 +495,7 @@ static void launch_m(const uint16_t* x, int mrows, int K, const uint16_t* W, int
             }
             GV(kResid, false, RP, N / RP, N, 0);
         } else {
-            const int r = M == 1 ? rows_knob(WQ ? "gemv_q_r_rope" : "gemv_r_rope", WQ ? 8 : 4) : 8;
+            const int r = M == 1 ? rows_knob(WM == kW8 ? "gemv_q_r_rope" : WM == kW4 ? "gemv_w4_r_rope" : "gemv_r_rope", WQ ? 8 : 4) : 8;
             if (mode == kRope) {
                 if (r == 4) {
                     if (np) GV(kRope, true, 4, N / 4, N, 0); else GV(kRope, false, 4, N / 4, N, 0);
@@ -465,20 +529,26 @@ void launch_gemv(const uint16_t* x, int M, int K, const uint16_t* W, int N, uint
 }
 
 void launch_gemv_ex(const uint16_t* x, int M, int K, const uint16_t* W, int N, uint16_t* y, bool swiglu,
-                    const GemvNorm* nrm, const GemvRope* rope, bool fp8, hipStream_t st, const float* wscale) {
+                    const GemvNorm* nrm, const GemvRope* rope, bool fp8, hipStream_t st, const float* wscale,
+                    const uint8_t* wexp) {
     if (M <= 0) return;
     const int mode = rope ? (fp8 ? kRope8 : kRope) : swiglu ? kSwiglu : kPlain;
+    if (wexp) {
+        if (M == 1) launch_m<1, kW4>(x, M, K, W, N, y, mode, nrm, rope, st, nullptr, wexp);
+        else launch_m<2, kW4>(x, M, K, W, N, y, mode, nrm, rope, st, nullptr, wexp);
+        return;
+    }
     if (wscale) {
-        if (M == 1) launch_m<1, true>(x, M, K, W, N, y, mode, nrm, rope, st, wscale);
-        else launch_m<2, true>(x, M, K, W, N, y, mode, nrm, rope, st, wscale);
+        if (M == 1) launch_m<1, kW8>(x, M, K, W, N, y, mode, nrm, rope, st, wscale);
+        else launch_m<2, kW8>(x, M, K, W, N, y, mode, nrm, rope, st, wscale);
         return;
     }
     if (M == 1) launch_m<1>(x, M, K, W, N, y, mode, nrm, rope, st);
     else launch_m<2>(x, M, K, W, N, y, mode, nrm, rope, st);
 }
 
-int gemv_resid_parts(int M, int N, bool wq) {
-    return N / (M == 1 ? resid_rows(N, wq) : M <= 2 ? rows_plain<2>() : rows_plain<4>());
+int gemv_resid_parts(int M, int N, int wmode) {
+    return N / (M == 1 ? resid_rows(N, wmode) : M <= 2 ? rows_plain<2>() : rows_plain<4>());
 }
 
 void launch_gemv_q(const uint16_t* x, int M, int K, const uint8_t* W, const float* wscale, int N, uint16_t* y,
@@ -486,24 +556,37 @@ void launch_gemv_q(const uint16_t* x, int M, int K, const uint8_t* W, const floa
     if (M <= 0) return;
     const uint16_t* w = reinterpret_cast<const uint16_t*>(W);
     const int mode = swiglu ? kSwiglu : kPlain;
-    if (M == 1) launch_m<1, true>(x, M, K, w, N, y, mode, nullptr, nullptr, st, wscale);
-    else if (M == 2) launch_m<2, true>(x, M, K, w, N, y, mode, nullptr, nullptr, st, wscale);
-    else launch_m<4, true>(x, M, K, w, N, y, mode, nullptr, nullptr, st, wscale);
+    if (M == 1) launch_m<1, kW8>(x, M, K, w, N, y, mode, nullptr, nullptr, st, wscale);
+    else if (M == 2) launch_m<2, kW8>(x, M, K, w, N, y, mode, nullptr, nullptr, st, wscale);
+    else launch_m<4, kW8>(x, M, K, w, N, y, mode, nullptr, nullptr, st, wscale);
+}
+
+void launch_gemv_w4(const uint16_t* x, int M, int K, const uint8_t* W, const uint8_t* wexp, int N, uint16_t* y,
+                    bool swiglu, hipStream_t st) {
+    if (M <= 0) return;
+    const uint16_t* w = reinterpret_cast<const uint16_t*>(W);
+    const int mode = swiglu ? kSwiglu : kPlain;
+    if (M == 1) launch_m<1, kW4>(x, M, K, w, N, y, mode, nullptr, nullptr, st, nullptr, wexp);
+    else if (M == 2) launch_m<2, kW4>(x, M, K, w, N, y, mode, nullptr, nullptr, st, nullptr, wexp);
+    else launch_m<4, kW4>(x, M, K, w, N, y, mode, nullptr, nullptr, st, nullptr, wexp);
 }
 
 int launch_gemv_resid(const uint16_t* x, int M, int K, const uint16_t* W, int N, const uint16_t* rin, uint16_t* rout,
-                      float* part_out, hipStream_t st, const float* wscale) {
+                      float* part_out, hipStream_t st, const float* wscale, const uint8_t* wexp) {
     if (M <= 0) return 0;
     GemvNorm nrm{};
     nrm.rin = rin;
     nrm.rout = rout;
     nrm.part_out = part_out;
-    if (wscale) {
-        if (M == 1) launch_m<1, true>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st, wscale);
-        else launch_m<2, true>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st, wscale);
+    if (wexp) {
+        if (M == 1) launch_m<1, kW4>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st, nullptr, wexp);
+        else launch_m<2, kW4>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st, nullptr, wexp);
+    } else if (wscale) {
+        if (M == 1) launch_m<1, kW8>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st, wscale);
+        else launch_m<2, kW8>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st, wscale);
     } else if (M == 1) launch_m<1>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st);
     else launch_m<2>(x, M, K, W, N, nullptr, kResid, &nrm, nullptr, st);
-    return gemv_resid_parts(M, N, wscale != nullptr);
+    return gemv_resid_parts(M, N, wexp ? kW4 : wscale ? kW8 : kW16);
 }
 
 }  // namespace chronos

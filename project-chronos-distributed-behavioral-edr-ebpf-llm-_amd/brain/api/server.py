@@ -144,10 +144,11 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
 
     def _model_entry():
         info = backend.info() if hasattr(backend, "info") else {}
+        quant = {"bf16": "BF16", "fp8": "FP8", "mxfp4": "MXFP4"}[getattr(backend, "weight_dtype", "bf16")]
         return {"name": f"{model_name}:latest", "model": f"{model_name}:latest", "modified_at": now_iso(),
                 "size": int(info.get("params", 0)) * 2, "digest": "chronos-random-init",
                 "details": {"format": "safetensors", "family": "llama", "families": ["llama"],
-                            "parameter_size": f"{info.get('params', 0) / 1e9:.1f}B", "quantization_level": "BF16"}}
+                            "parameter_size": f"{info.get('params', 0) / 1e9:.1f}B", "quantization_level": quant}}
 
     async def tags(request):
         return web.json_response({"models": [_model_entry()]})
@@ -231,7 +232,7 @@ class FakeBackend:
 # ---------------------------------------------------------------------------------------------------------------
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="CHRONOS Brain: Ollama-compatible Llama-3 server on MI355X")
     ap.add_argument("--host", default="0.0.0.0")
     ap.add_argument("--port", type=int, default=11434)
@@ -254,13 +255,20 @@ def main(argv=None) -> int:
     ap.add_argument("--request-timeout", type=float, default=0.0,
                     help="seconds; a slower generation answers 504 and is cancelled in the engine (0 = none)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                    help="projection weights: bf16, fp8 (W8A8 e4m3) or mxfp4 (OCP MXFP4 for the low-batch decode GEMV, "
+                         "with a resident bf16 copy for every other kernel)")
     ap.add_argument("--max-logprobs", type=int, default=20,
                     help="most top_logprobs a request may ask for (0-20); 0 = logprobs are not offered")
     ap.add_argument("--penalty-window", type=int, default=64,
                     help="history window of repeat / frequency / presence penalties, the most repeat_last_n can "
                          "reach (0-1024); 0 = penalties are not offered")
     ap.add_argument("--roctx", action="store_true", help="emit roctx ranges for rocprofv3 --marker-trace")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
     if a.roctx:
         from ...utils import trace
 
@@ -274,6 +282,7 @@ def main(argv=None) -> int:
 
         cfg = EngineConfig(model=a.model, checkpoint=a.checkpoint, tokenizer=a.tokenizer, device=a.device,
                            max_slots=a.max_slots, max_model_len=a.max_model_len, kv_dtype=a.kv_dtype,
+                           weight_dtype=a.weights,
                            request_timeout_s=a.request_timeout, tp_sequence_parallel=a.sequence_parallel,
                            max_logprobs=a.max_logprobs, penalty_window=a.penalty_window)
         if a.tp > 1 or a.cp > 1:

@@ -47,6 +47,10 @@ class EngineService:
     def tok(self):
         return self.engine.tok
 
+    @property
+    def weight_dtype(self) -> str:
+        return self.engine.cfg.weight_dtype
+
     @classmethod
     def from_config(cls, cfg: EngineConfig, model_name: str = "llama3") -> "EngineService":
         return cls(Engine(cfg), model_name)

@@ -90,7 +90,10 @@ class EngineConfig:
     prefix_cache: bool = True      # reuse KV blocks of identical prompt prefixes (the shared CHRONOS template head)
     partial_prefix: bool = True    # ... and the computed leading slots of a partially matching block (copied in)
     kv_dtype: str = "bf16"         # "bf16" or "fp8" (OCP e4m3fn, per-layer scale: half the KV bytes, 2x tokens/GPU)
-    weight_dtype: str = "bf16"     # "bf16" or "fp8": W8A8 e4m3 projections on the block-scaled MFMA (csrc/kernels/fp8.hip)
+    # "bf16"; "fp8": W8A8 e4m3 projections on the block-scaled MFMA (csrc/kernels/fp8.hip); "mxfp4": OCP MXFP4
+    # projections for the W4A16 single-stream decode GEMV (csrc/kernels/gemv.hip W4) plus a resident bf16 copy for every
+    # other kernel — a latency mode: bf16 + ~0.27 of it again in memory
+    weight_dtype: str = "bf16"
     kv_scale: float = 1.0          # fp8 KV scale (stored = value / scale)
     prefill_nqt: int = 8           # 8 = flash prefill kernel (128 query rows / workgroup); 1-2 = split-K kernel
     async_harvest: bool = False    # harvest burst k while burst k+1 runs (hides host work, delays compaction)

@@ -189,13 +189,42 @@ def quantize(w: torch.Tensor) -> QTensor:
 
 
 @dataclass
+class Q4Tensor:
+    """OCP MXFP4 projection weight (ops.reference.quantize_mxfp4): packed e2m1 ``q`` [N, K / 2] uint8, e8m0 block
+    scales ``e`` [N, K / 32] uint8, and ``w``, the same weights dequantised to bf16 [N, K] (exact).  The W4A16 decode
+    GEMV (csrc/kernels/gemv.hip W4) streams q and e where it measured faster (M = 1, ops/gemm.py W4_MAX_M); every
+    other path — prefill, batched decode, TP / SP / CP, the CPU reference — runs the bf16 kernels on ``w``: the same
+    mathematical product.  Quantised after TP
+    sharding like QTensor, so a row-parallel shard's MX blocks lie inside its own K-slice.  It has no ``s`` field, so
+    ``ops.is_q`` is false for it and everything that asks ``LlamaWeights.fp8`` treats the model as bf16."""
+    q: torch.Tensor
+    e: torch.Tensor
+    w: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.w.shape
+
+    def numel(self) -> int:
+        return self.w.numel()
+
+    def nbytes(self) -> int:
+        return self.q.numel() + self.e.numel() + 2 * self.w.numel()
+
+
+def quantize_mxfp4(w: torch.Tensor) -> Q4Tensor:
+    q, e = ops.reference.quantize_mxfp4(w)
+    return Q4Tensor(q, e, ops.reference.dequantize_mxfp4(q, e))
+
+
+@dataclass
 class LayerWeights:
     attn_norm: torch.Tensor
-    wqkv: "torch.Tensor | QTensor"
-    wo: "torch.Tensor | QTensor"
+    wqkv: "torch.Tensor | QTensor | Q4Tensor"
+    wo: "torch.Tensor | QTensor | Q4Tensor"
     mlp_norm: torch.Tensor
-    w_gu: "torch.Tensor | QTensor"
-    w_down: "torch.Tensor | QTensor"
+    w_gu: "torch.Tensor | QTensor | Q4Tensor"
+    w_down: "torch.Tensor | QTensor | Q4Tensor"
 
 
 @dataclass
@@ -213,12 +242,16 @@ class LlamaWeights:
         n = 2 * (self.embed.numel() + self.norm.numel() + (0 if self.lm_head is self.embed else self.lm_head.numel()))
         for l in self.layers:
             for t in (l.attn_norm, l.wqkv, l.wo, l.mlp_norm, l.w_gu, l.w_down):
-                n += t.nbytes() if isinstance(t, QTensor) else 2 * t.numel()
+                n += t.nbytes() if isinstance(t, (QTensor, Q4Tensor)) else 2 * t.numel()
         return n
 
     @property
     def fp8(self) -> bool:
         return bool(self.layers) and isinstance(self.layers[0].wqkv, QTensor)
+
+    @property
+    def w4(self) -> bool:
+        return bool(self.layers) and isinstance(self.layers[0].wqkv, Q4Tensor)
 
 
 def _shard_rows(t: torch.Tensor, rank: int, world: int) -> torch.Tensor:
@@ -248,7 +281,8 @@ def fold_norm(wt: torch.Tensor, nw: torch.Tensor) -> torch.Tensor:
 def assemble_layer(cfg: LlamaConfig, tp: TPContext, full: dict, device, dtype=torch.bfloat16,
                    weight_dtype: str = "bf16", fold_norms: bool = True) -> LayerWeights:
     """Full (unsharded) HF-named tensors of one layer -> this rank's fused shard (projections quantised to
-    per-channel e4m3 when ``weight_dtype == "fp8"``; norms stay bf16).  ``fold_norms``: the input-norm weights are
+    per-channel e4m3 when ``weight_dtype == "fp8"``, to MXFP4 with a resident bf16 copy when ``"mxfp4"``; norms stay
+    bf16).  ``fold_norms``: the input-norm weights are
     folded into QKV / gate_up (before quantisation) and stored as ones."""
     if fold_norms:
         full = dict(full)
@@ -275,10 +309,12 @@ def assemble_layer(cfg: LlamaConfig, tp: TPContext, full: dict, device, dtype=to
     cv = lambda t: t.to(device=device, dtype=dtype).contiguous()  # noqa: E731
     if weight_dtype == "fp8":
         pj = lambda t: quantize(cv(t))  # noqa: E731
+    elif weight_dtype == "mxfp4":
+        pj = lambda t: quantize_mxfp4(cv(t))  # noqa: E731
     elif weight_dtype == "bf16":
         pj = cv
     else:
-        raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
     return LayerWeights(cv(full["attn_norm"]), pj(wqkv), pj(wo), cv(full["mlp_norm"]), pj(w_gu), pj(w_down))
 
 
@@ -867,7 +903,8 @@ def build_model(preset: str | LlamaConfig = "tiny", device="cpu", tp: TPContext 
                 checkpoint: str | None = None, max_position: int | None = None,
                 weight_dtype: str = "bf16") -> LlamaModel:
     """``weight_dtype="fp8"``: projections as per-channel e4m3 + W8A8 fp8 MFMA GEMMs (embedding, norms, LM head, attention
-    and the KV cache keep their own dtypes)."""
+    and the KV cache keep their own dtypes).  ``"mxfp4"``: projections as OCP MXFP4 for the W4A16 decode GEMV plus their
+    bf16 dequantisation for every other kernel (Q4Tensor)."""
     tp = tp or TPContext.single()
     if checkpoint:
         cfg, w = load_checkpoint(checkpoint, tp, device, weight_dtype)

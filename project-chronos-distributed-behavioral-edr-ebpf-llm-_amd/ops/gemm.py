@@ -266,6 +266,38 @@ def gemv_q_ok(m: int, n: int, k: int) -> bool:
     return m <= 4 and k % 1024 == 0 and n % 16 == 0
 
 
+# W4A16 decode: a Q4Tensor (models/llama.py: OCP MXFP4 q / e plus the dequantised bf16 copy w) takes the fp4 GEMV
+# (gemv.hip W4) at its shapes and everything else runs the bf16 kernels on ``.w`` — the same product.  Env
+# CHRONOS_W4A16_DECODE=0 (or this flag) forces ``.w`` everywhere: the A/B switch, and what the tests compare against.
+_W4A16_DECODE = os.environ.get("CHRONOS_W4A16_DECODE", "1") != "0"
+# Largest M routed to the fp4 kernel (env CHRONOS_W4_MAX_M; the kernel takes up to 4).  Only what wins is routed:
+# on cold 8B weights the fp4 GEMV beats the bf16 GEMV on ``.w`` 1.30-1.75x at M = 1 on all four projections, and at
+# M = 2 and M = 4 it loses on all four, to the bf16 GEMV (0.57-0.90x) and more so to the skinny MFMA GEMM that ``.w``
+# is routed to there (0.29-0.79x) — scripts/bench_gemv_w4.py, profiles/mxfp4/gemv_table.jsonl.  So two-stream decode and
+# jump-forward chunks run on ``.w``; the tests raise this to reach the M = 2..4 instantiations.
+W4_MAX_M = int(os.environ.get("CHRONOS_W4_MAX_M", "1"))
+w4_stats = {"gemv_launches": 0}  # fp4 GEMV launches issued from Python (captured graphs replay them uncounted)
+
+
+def is_w4(w) -> bool:
+    """An MXFP4 projection weight (models/llama.py Q4Tensor: packed e2m1 ``q``, e8m0 ``e``, bf16 copy ``w``)."""
+    return not isinstance(w, torch.Tensor) and hasattr(w, "q") and hasattr(w, "e") and hasattr(w, "w")
+
+
+def gemv_w4_ok(m: int, n: int, k: int) -> bool:
+    """Shapes of the W4A16 decode GEMV (gemv.hip W4: mxfp4 weights, bf16 activations): up to 4 rows (the fused
+    norm / RoPE / residual epilogues: 2), whole 1024-element chunks (32 MX blocks), 16 rows per group."""
+    return 1 <= m <= 4 and k % 1024 == 0 and n % 16 == 0
+
+
+def _w4_route(t: torch.Tensor, m: int, n: int, k: int, mmax: int = 4) -> bool:
+    """True: the fp4 kernel takes this call (and is counted); False: the caller substitutes ``w.w``."""
+    if not (_W4A16_DECODE and t.is_cuda and m <= min(mmax, W4_MAX_M) and gemv_w4_ok(m, n, k)):
+        return False
+    w4_stats["gemv_launches"] += 1
+    return True
+
+
 def _q_fallback(x, w, swiglu: bool = False) -> torch.Tensor:
     """fp8 weight off the W8A16 GEMV shapes: quantise the activations and run the W8A8 op."""
     from . import qlinear, quant_rows
@@ -282,6 +314,14 @@ def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOu
     from . import _k
 
     m, k = x.numel() // x.shape[-1], x.shape[-1]
+    if is_w4(w):
+        # the fp4 producer at the W8A16 precedent's rows (M <= min(GEMV_MAX_M, 2)); 8 rows per group: N / 8 partials,
+        # which the consumer reads as float4
+        if w.shape[0] % 32 == 0 and _w4_route(x, m, w.shape[0], k, min(GEMV_MAX_M, 2)):
+            s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
+            part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, None, w.e)
+            return ResidOut(s, part)
+        w = w.w
     if is_q(w):
         s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
         part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, w.s)
@@ -296,7 +336,9 @@ def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOu
 
 def resid_ok(m: int, n: int, k: int, fp8: bool = False) -> bool:
     """Shapes of the residual-epilogue producer: the M <= 2 GEMV shapes (gemv.hip kResid) and the batched GEMM's
-    (gemm_pp.hip kResid) where the plan takes it; fp8 weights: the W8A16 GEMV shapes only."""
+    (gemm_pp.hip kResid) where the plan takes it; fp8 weights: the W8A16 GEMV shapes only.  An mxfp4 Q4Tensor asks
+    as bf16 (fp8=False): ``gemv_resid`` runs its fp4 producer where that takes the shape and the bf16 one on ``.w``
+    otherwise, so whatever is true for bf16 is true for it."""
     if fp8:
         return m <= min(GEMV_MAX_M, 2) and gemv_q_ok(m, n, k)
     if m <= GEMV_MAX_M:
@@ -338,6 +380,17 @@ def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
     SwiGLU epilogue above, with the folded input norm when x is a LazyNorm), else GEMM + silu_mul."""
     from . import _k, silu_mul
 
+    if is_w4(w_gu):  # mxfp4 weights: the W4A16 GEMV at its shapes, else the bf16 copy through the code below
+        lazy = isinstance(x, LazyNorm)
+        t = x.s if lazy else x
+        m, n, k = t.numel() // t.shape[-1], w_gu.shape[0], t.shape[-1]
+        if _w4_route(t, m, n, k):
+            if lazy and x.fusable() and m <= 2:
+                return _k().gemv_normp(x.s, x.part, x.eps, w_gu.q, True, None, w_gu.e)
+            x = LazyNorm.force(x)
+            y = _k().gemv(x.reshape(-1, k), w_gu.q, True, None, w_gu.e)
+            return y.view(*x.shape[:-1], y.shape[-1])
+        w_gu = w_gu.w
     if is_q(w_gu):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
         m, n, k = (x.rows() if isinstance(x, LazyNorm) else x.numel() // x.shape[-1]), w_gu.shape[0], x.shape[-1]
         if isinstance(x, LazyNorm) and x.fusable() and m <= 2 and gemv_q_ok(m, n, k):
@@ -370,6 +423,19 @@ def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
 
 
 def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if is_w4(w):  # mxfp4 weights: the W4A16 GEMV at its shapes, else the bf16 copy through the code below
+        lazy = isinstance(x, LazyNorm)
+        t = x.s if lazy else x
+        m, n, k = t.numel() // t.shape[-1], w.shape[0], t.shape[-1]
+        if out is None and _w4_route(t, m, n, k):
+            from . import _k
+
+            if lazy and x.fusable() and m <= 2:
+                return _k().gemv_normp(x.s, x.part, x.eps, w.q, False, None, w.e)
+            x = LazyNorm.force(x)
+            y = _k().gemv(x.reshape(-1, k), w.q, False, None, w.e)
+            return y.view(*x.shape[:-1], n)
+        w = w.w
     if is_q(w):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
         from . import _k
 

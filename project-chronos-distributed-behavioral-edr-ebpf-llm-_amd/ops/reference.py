@@ -92,6 +92,50 @@ def quantize_weight(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q.contiguous(), s.contiguous()
 
 
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # e2m1 magnitudes by code bits 0-2
+
+
+def quantize_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """OCP Microscaling (MX) v1.0 MXFP4 weight quantisation of w [N, K] (K % 32 == 0):
+    (q uint8 [N, K / 2], e uint8 [N, K / 32]).
+
+    * One e8m0 scale per block of 32 consecutive K elements: the shared exponent is X = floor(log2(amax)) - 2 (2 =
+      e2m1's largest exponent), stored as e = X + 127 clamped to [1, 254], so that the scale 2^(e - 127) is an f32
+      normal whose bit pattern is ``e << 23`` (what the decode GEMV feeds v_cvt_scalef32_pk_bf16_fp4).  An all-zero
+      block takes e = 127.
+    * Elements are w / 2^X, saturated to +-6, rounded to the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6} to nearest, ties
+      to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4).
+    * A code is sign in bit 3, magnitude index in bits 0-2; element 2i is the low nibble of byte i, element 2i + 1
+      the high nibble.
+
+    Every dequantised value (a 1-bit mantissa times a power of two) is exactly representable in bf16."""
+    n, k = w.shape
+    assert k % 32 == 0, "mxfp4: K must be a multiple of the 32-element MX block"
+    wf = w.float().reshape(n, k // 32, 32)
+    amax = wf.abs().amax(-1)
+    _, ex = torch.frexp(amax)  # amax = m * 2^ex with m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax > 0, (ex - 3 + 127).clamp(1, 254), torch.full_like(ex, 127)).to(torch.int32)
+    scale = (e << 23).view(torch.float32)
+    a = (wf.abs() / scale[..., None]).clamp(max=6.0)
+    idx = ((a > 0.25).int() + (a >= 0.75).int() + (a > 1.25).int() + (a >= 1.75).int() + (a > 2.5).int()
+           + (a >= 3.5).int() + (a > 5.0).int())
+    code = (idx | (torch.signbit(wf).int() << 3)).reshape(n, k // 2, 2)
+    q = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)
+    return q.contiguous(), e.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(q: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """bf16 [N, K] of MXFP4 (q [N, K / 2], e [N, K / 32]) as written by ``quantize_mxfp4``: grid[code] * 2^(e - 127),
+    exact in bf16."""
+    n, k = q.shape[0], q.shape[1] * 2
+    qi = q.to(torch.int32)
+    code = torch.stack([qi & 15, qi >> 4], -1).reshape(n, k // 32, 32)
+    mag = torch.tensor(MXFP4_GRID, dtype=torch.float32, device=q.device)[(code & 7).long()]
+    val = torch.where((code & 8) != 0, -mag, mag)
+    scale = (e.to(torch.int32) << 23).view(torch.float32)
+    return (val * scale[..., None]).reshape(n, k).to(torch.bfloat16).contiguous()
+
+
 def rope_kv_write(qkv, pos, tok_seq, block_table, cos_sin, q_out, k_cache, v_cache, hq: int, hkv: int,
                   write_q: bool = True, k_scale: float = 1.0, v_scale: float = 1.0) -> None:
     T = qkv.shape[0]

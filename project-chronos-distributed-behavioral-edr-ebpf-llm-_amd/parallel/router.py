@@ -124,6 +124,7 @@ class DPRouter:
         self._dev = device or ("cuda" if str(cfg.device).startswith("cuda") else "cpu")
         self._ctx = mp.get_context("spawn")
         self._cfgd = asdict(cfg)
+        self.weight_dtype = cfg.weight_dtype  # what /api/tags reports as quantization_level
         self._res = self._ctx.Queue()
         self._reqs = [self._ctx.Queue() for _ in range(replicas)]
         self._ready_seen = [False] * replicas  # the current process of each replica reported ready

@@ -46,7 +46,7 @@ def main():
     ap.add_argument("--rows", type=int, default=128)
     ap.add_argument("--ctx", type=int, default=200)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "mxfp4"])
     ap.add_argument("--knob", action="append", default=[], help="kernel knob name=value (torch.ops.chronos.set_knob)")
     ap.add_argument("--tp-rank-of", type=int, default=1, help="W > 1: one rank of a W-way TP model, local collectives")
     a = ap.parse_args()

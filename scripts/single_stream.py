@@ -33,7 +33,7 @@ def main():
     ap.add_argument("--only", choices=list(VARIANTS), default="fused", help="variant without --ab")
     ap.add_argument("--knob-ab", default=None,
                     help="';'-separated knob sets ('name=v,name=v'), one fused engine captured under each, interleaved")
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
