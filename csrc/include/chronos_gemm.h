@@ -21,6 +21,9 @@ struct PPArgs {
     const float* xsc;  // gemm_lg F8 (W8A8 e4m3fn bytes in x / w): per-token scales [M]
     const float* wsc;  // ... and per-output-channel scales [N]
     int ablate;  // timing-only diagnostics (knob pp_ablate): 1 skip loop DMA, 2 skip LDS reads, 4 skip MFMA, 8 nt weights, 16/32 alias every W/x tile onto tile 0
+    // gemm_skinny W4A16: e8m0 block scales [N, K / 32] of the packed e2m1 bytes in w.  Last, so that every other
+    // field keeps its kernel-argument offset; bf16 callers leave it null.
+    const uint8_t* wexp = nullptr;
 };
 
 // epilogue modes
@@ -57,5 +60,12 @@ int gemm_skinny_rt(int cfg);
 int gemm_skinny_mt(int cfg);
 int gemm_skinny_nw(int cfg);  // waves per workgroup
 bool launch_gemm_skinny(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st);
+// ... and its W4A16 weight mode (OCP MXFP4: a.w = packed e2m1 [N, K / 2], a.wexp = e8m0 [N, K / 32]; x, y, resid,
+// partials, slabs and tickets as above), own config ids: M <= 16 * MT, K % (128 * NW * splitk) == 0
+constexpr int kSkinnyW4Configs = 13;
+int gemm_skinny_w4_rt(int cfg);
+int gemm_skinny_w4_mt(int cfg);
+int gemm_skinny_w4_nw(int cfg);
+bool launch_gemm_skinny_w4(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st);
 
 }  // namespace chronos

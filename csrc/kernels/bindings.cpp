@@ -793,28 +793,53 @@ std::tuple<Tensor, Tensor> gemm_pp(const Tensor& x, const Tensor& w, int64_t mod
 }
 
 // Skinny-M GEMM (gemm_skinny.hip), M <= 16 * MT of the config: same epilogues and tensors as gemm_pp; the kResid
-// partials are [M, N / (16 * RT)].
+// partials are [M, N / (16 * RT)].  With ``we`` the W4A16 weight mode: w = packed e2m1 bytes [N, K / 2], we = e8m0 block
+// scales [N, K / 32] (OCP MXFP4), cfg an id of the W4 config table, K % (128 * NW * splitk) == 0.
 std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t mode, int64_t cfg, int64_t splitk,
                                        const c10::optional<Tensor>& resid, const c10::optional<Tensor>& part_in,
-                                       double eps) {
+                                       double eps, const c10::optional<Tensor>& we) {
     chk_bf16(x, "x");
-    chk_bf16(w, "w");
+    const bool w4 = we.has_value();
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
-    CHK(w.dim() == 2 && w.size(1) == K, "gemm_skinny: w must be [N, K]");
-    CHK(cfg >= 0 && cfg < chronos::kSkinnyConfigs, "gemm_skinny: cfg");
+    if (w4) {
+        chk_gpu(w, "w");
+        chk_gpu(*we, "we");
+        CHK(w.scalar_type() == at::kByte && w.dim() == 2 && K % 32 == 0 && w.size(1) == K / 2,
+            "gemm_skinny: mxfp4 w must be uint8 [N, K / 2]");
+        CHK(we->scalar_type() == at::kByte && we->dim() == 2 && we->size(0) == N && we->size(1) == K / 32,
+            "gemm_skinny: we must be uint8 [N, K / 32]");
+        CHK(w.is_contiguous() && we->is_contiguous() && w.device() == x.device() && we->device() == x.device(),
+            "gemm_skinny: w / we contiguous, on x's device");
+        CHK(cfg >= 0 && cfg < chronos::kSkinnyW4Configs, "gemm_skinny: W4 cfg");
+    } else {
+        chk_bf16(w, "w");
+        CHK(w.dim() == 2 && w.size(1) == K, "gemm_skinny: w must be [N, K]");
+        CHK(cfg >= 0 && cfg < chronos::kSkinnyConfigs, "gemm_skinny: cfg");
+    }
     CHK(mode >= 0 && mode <= 2, "gemm_skinny: mode");
-    const int RT = chronos::gemm_skinny_rt((int)cfg), MT = chronos::gemm_skinny_mt((int)cfg);
-    const int NW = chronos::gemm_skinny_nw((int)cfg);
+    const int RT = w4 ? chronos::gemm_skinny_w4_rt((int)cfg) : chronos::gemm_skinny_rt((int)cfg);
+    const int MT = w4 ? chronos::gemm_skinny_w4_mt((int)cfg) : chronos::gemm_skinny_mt((int)cfg);
+    const int NW = w4 ? chronos::gemm_skinny_w4_nw((int)cfg) : chronos::gemm_skinny_nw((int)cfg);
     CHK(M >= 1 && M <= 16 * MT, "gemm_skinny: M must be in [1, 16 * MT] of the config");
-    CHK(splitk >= 1 && K % (64 * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
-        "gemm_skinny: K % (64 * NW * splitk) == 0");
+    if (w4) {
+        CHK(splitk >= 1 && K % (128 * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
+            "gemm_skinny: W4 K % (128 * NW * splitk) == 0");
+    } else {
+        CHK(splitk >= 1 && K % (64 * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
+            "gemm_skinny: K % (64 * NW * splitk) == 0");
+    }
     CHK(mode == 1 ? RT % 2 == 0 && (N / 2) % (8 * RT) == 0 && N % 2 == 0 : N % (16 * RT) == 0,
         "gemm_skinny: N % (16 RT) (swiglu: F % (8 RT), RT even)");
     CHK(mode != 2 || !part_in.has_value(), "gemm_skinny: resid mode has no norm prologue");
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     chronos::PPArgs a{};
     a.x = bf(x);
-    a.w = bf(w);
+    if (w4) {
+        a.w = reinterpret_cast<const uint16_t*>(w.data_ptr<uint8_t>());
+        a.wexp = we->data_ptr<uint8_t>();
+    } else {
+        a.w = bf(w);
+    }
     a.M = (int)M;
     a.N = (int)N;
     a.K = (int)K;
@@ -845,7 +870,12 @@ std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t
         a.ws = ws.data_ptr<float>();
         a.cnt = split_tickets(x, groups);
     }
-    CHK(chronos::launch_gemm_skinny((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()), "gemm_skinny: launch");
+    if (w4) {
+        CHK(chronos::launch_gemm_skinny_w4((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()),
+            "gemm_skinny: W4 launch");
+    } else {
+        CHK(chronos::launch_gemm_skinny((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()), "gemm_skinny: launch");
+    }
     return {y, part_out};
 }
 
@@ -1013,7 +1043,7 @@ TORCH_LIBRARY(chronos, m) {
     m.def("gemv(Tensor x, Tensor w, bool swiglu, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("gemm(Tensor x, Tensor w, bool swiglu, int stages=3) -> Tensor");
     m.def("gemm_pp(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, bool prio) -> (Tensor, Tensor)");
-    m.def("gemm_skinny(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps) "
+    m.def("gemm_skinny(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, Tensor? we=None) "
           "-> (Tensor, Tensor)");
     m.def("gemv_resid(Tensor x, Tensor w, Tensor resid_in, Tensor(a!) resid_out, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("gemv_normp(Tensor s, Tensor part, float eps, Tensor w, bool swiglu, Tensor? ws=None, Tensor? we=None) -> Tensor");

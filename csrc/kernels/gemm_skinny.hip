@@ -23,6 +23,16 @@
 //     fp32 slabs and an agent-scope ticket whose last arriver sums the slabs in slice order (no fences; bitwise
 //     reproducible, graph == eager);
 //   * epilogue per (row m, 4 consecutive outputs): 8-byte stores, CPR consecutive lanes cover a row's 16 RT outputs.
+//
+// W4A16 weight mode (WM = kW4, M <= 64: jump-forward chunks and 2-64 stream decode of an mxfp4 model): the same
+// kernel with the main loop replaced by w4_stream below — W arrives as OCP MXFP4 (PPArgs.w = packed e2m1 [N, K / 2],
+// PPArgs.wexp = e8m0 [N, K / 32], 4.25 bits per weight), is converted in registers (exact) and feeds the same bf16
+// MFMA, accumulators, cross-wave reduction, split-K hand-off and epilogues; own config table (SK4_CONFIGS).  The bf16
+// instantiations compile to the instructions they had before the mode existed (NU = 0 makes the bf16 loop dead code
+// in a W4 instantiation instead of moving it into a branch, which changed the bf16 register allocation).
+// On cold 8B weights (scripts/bench_skinny_w4.py, profiles/mxfp4/skinny_table.jsonl; the figures are in the README)
+// it beats the bf16 kernel that the dequantised copy is routed to at M = 2-32 on all four projections, by less at
+// M = 48 / 64 on O and down, and not at QKV and gate_up there, which stay on the copy (ops/gemm_plan.json "w4plans").
 #include <algorithm>
 
 #include "chronos_gemm.h"
@@ -32,11 +42,143 @@ namespace chronos {
 namespace {
 
 enum : int { kPlain = kPPPlain, kSwiglu = kPPSwiglu, kResid = kPPResid };
+// weight mode: bf16 | packed e2m1 + e8m0 block scales (W4A16, OCP MXFP4: PPArgs w = q bytes, wexp = e bytes)
+enum : int { kW16 = 0, kW4 = 2 };
 constexpr int XL_MIN_MT = 2;  // x staged through LDS from MT = 2 (x bytes >= the weight bytes per wave)
 
-template <int RT, int MT, int D, int NW, int MODE, bool NORMP>
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// W4A16 main loop (WM = kW4): the same workgroup, accumulators, reduction and epilogues, with W streamed as OCP MXFP4
+// (q [N, K / 2] packed e2m1, element 2i in the low nibble of byte i; e [N, K / 32] e8m0) — 0.27 of the bf16 bytes.
+//   * unit = 128 k.  Lane l (r = l & 15, q = l >> 4) loads the 16-B piece that is MX block k0 / 32 + q of row r — 32
+//     elements, one scale byte — and MFMA step i = 0..3 takes the four v_cvt_scalef32_pk_bf16_fp4 of dword i (the e8m0
+//     byte as the f32 exponent: exact, as in gemv.hip q4bf) as its A operand: k0 + 32 q + 8 i .. + 8.  The B operand of
+//     the lane with x row n and the same q is x[n][k0 + 32 q + 8 i .. + 8]: both sides put the same k into the same
+//     MFMA slot, and after 4 MFMAs the unit's 128 k were each used once (a dot product does not care about k order);
+//   * a wave's K range is contiguous (wave w: KS / NW from s KS + w KS / NW on), not interleaved in units like the bf16
+//     loop: a unit touches half a 128-B line of each of its 16 rows and the same wave's next unit, which is in flight
+//     with it in the ring (D >= 2), touches the other half.  It also keeps the divisibility at K % (128 NW splitk),
+//     which 16 waves meet at K = 14336; a 256-k unit of two pieces would not;
+//   * x per unit is 16 MT rows x 256 B, four times what the bf16 loop reads per weight byte.  Without XL a lane loads
+//     its four B operands directly (64 contiguous bytes: per instruction 16 rows x 4 pieces of 16 B, 64 B apart);
+//     with XL the unit's x tile comes in whole rows (lane l: row 4 j + l / 16, 16-B chunk l % 16 of the row's 256 B)
+//     and goes through the wave's LDS tile (slot chunk ^ (row & 15): both sides conflict-free) into the B layout;
+//   * ring stage = RT pieces (4 VGPRs) + RT scale bytes + 16 MT VGPRs of x.
+// hipcc -Rpass-analysis=kernel-resource-usage, per SK4_CONFIGS id (plain epilogue; the others within 4 VGPRs): no
+// config uses scratch.  VGPRs (+ AGPRs), waves per SIMD:  0: 178 + 16, 2;  1: 198 + 16, 2;  2: 160, 3;  3: 138, 3;
+// 4: 146, 3;  5: 88, 5;  6: 88, 5;  7: 208 + 32, 2;  8: 186, 2;  9: 186, 2;  10: 254 + 92, 1 (up to + 104 with NORMP);
+// 11: 242, 2;  12: 232 + 40, 1.
+// Subnormals: with e = 1 the products 0.5 .. 6 * 2^-127 are bf16 subnormals or just above; measured on gfx950
+// (tests/test_mxfp4_skinny_gpu.py prints it), a one-hot probe returns every one of the 16 codes exactly, 0.5 * 2^-126
+// included: neither the conversion nor the bf16 MFMA nor the f32 -> bf16 store flushes them.  The tests assert e >= 2.
+// The scale operand is the e8m0 byte moved into an f32 exponent field (e << 23, as gemv.hip q4bf), so the two end
+// codes are not representable this way: e = 0 (2^-127, an f32 subnormal) becomes 0.0 and e = 255 (the MX NaN code)
+// becomes inf.  ops.reference.quantize_mxfp4 emits neither.
+// Measured: XL at MT = 1 (ids 1, 4 against 0, 3) is within 3 % either way, so x is not bound by the load shape
+// there; plain instead of nontemporal weight loads gained 0-5 % on the 4-wave configs and nothing on the others and
+// were not kept.
+template <int RT, int MT, int D, int NW, int MODE, bool XL>
+__device__ __forceinline__ void w4_stream(const PPArgs& a, int g, int s, int KS, int lane, int wave,
+                                          unsigned char* smem, f32x4 (&acc)[RT][MT]) {
+    const int M = a.M, K = a.K;
+    const int KW = KS / NW;   // this wave's contiguous K range
+    const int NU = KW / 128;  // 128-k units per wave
+    const int kw = s * KS + wave * KW;
+    const int r = lane & 15, q = lane >> 4;
+    const unsigned char* wq = reinterpret_cast<const unsigned char*>(a.w);
+    const i32x4* wp[RT];
+    const unsigned char* ep[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        int row;
+        if constexpr (MODE == kSwiglu)
+            row = rt < RT / 2 ? g * 8 * RT + 16 * rt : a.F + g * 8 * RT + 16 * (rt - RT / 2);
+        else
+            row = g * 16 * RT + 16 * rt;
+        wp[rt] = reinterpret_cast<const i32x4*>(wq + (int64_t)(row + r) * (K / 2) + kw / 2 + 16 * q);
+        ep[rt] = a.wexp + (int64_t)(row + r) * (K / 32) + kw / 32 + q;
+    }
+    // x offsets in 16-B pieces from a.x (M K < 2^31 elements): XL 4 MT row pieces, else one per x tile
+    const bf16x8* xb = reinterpret_cast<const bf16x8*>(a.x);
+    constexpr int NX = XL ? 4 * MT : MT;
+    uint32_t xo[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+        if constexpr (XL)
+            xo[j] = (uint32_t)(((int64_t)min(4 * j + q, M - 1) * K + kw) / 8 + r);
+        else
+            xo[j] = (uint32_t)(((int64_t)min(16 * j + r, M - 1) * K + kw) / 8 + 4 * q);
+    }
+    unsigned char* xs = smem + wave * (MT * 4096);  // XL: this wave's x tile, 16 MT rows x 256 B
+
+    i32x4 wr[D][RT];
+    uint32_t er[D][RT];
+    bf16x8 xr[D][MT][4];
+    auto load = [&](int u, int d) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            wr[d][rt] = __builtin_nontemporal_load(wp[rt] + 4 * u);  // 128 k = 64 B
+            er[d][rt] = ep[rt][4 * u];
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)  // 128 k = 16 pieces
+                xr[d][mt][i] = XL ? xb[xo[4 * mt + i] + 16 * u] : xb[xo[mt] + 16 * u + i];
+    };
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+        if (d < NU) load(d, d);
+
+    for (int u0 = 0; u0 < NU; u0 += D) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int u = u0 + d;
+            if (u < NU) {
+                if constexpr (XL) {
+                    // row layout -> LDS -> MFMA layout (row 16 mt + r, chunk 4 q + i); LDS ops of a wave run in order
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int t = 4 * (4 * mt + i) + q;
+                            *reinterpret_cast<bf16x8*>(xs + t * 256 + ((r ^ (t & 15)) << 4)) = xr[d][mt][i];
+                        }
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int t = 16 * mt + r;
+                            xr[d][mt][i] = *reinterpret_cast<const bf16x8*>(xs + t * 256 + (((4 * q + i) ^ r) << 4));
+                        }
+                }
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                    const float sc = __builtin_bit_cast(float, er[d][rt] << 23);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int wi = wr[d][rt][i];
+                        const bf16x2 c0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi, sc, 0);
+                        const bf16x2 c1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi, sc, 1);
+                        const bf16x2 c2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi, sc, 2);
+                        const bf16x2 c3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wi, sc, 3);
+                        const bf16x8 wa = bf16x8{c0[0], c0[1], c1[0], c1[1], c2[0], c2[1], c3[0], c3[1]};
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+                            acc[rt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xr[d][mt][i], acc[rt][mt], 0, 0, 0);
+                    }
+                }
+                if (u + D < NU) load(u + D, d);
+            }
+        }
+    }
+}
+template <int RT, int MT, int D, int NW, int MODE, bool NORMP, int WM = kW16, bool XL4 = false>
 __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     static_assert(MODE != kSwiglu || RT % 2 == 0, "swiglu: RT/2 gate tiles + RT/2 up tiles");
+    constexpr bool W4 = WM == kW4;
+    constexpr bool XL = W4 ? XL4 : MT >= XL_MIN_MT;  // x through the wave's LDS tile (below; W4: per config)
     constexpr int NT = 64 * NW;                        // threads
     constexpr int UNITS = RT * MT * 64;                // f32x4 accumulators per wave
     constexpr int CPR = MODE == kSwiglu ? 2 * RT : 4 * RT;  // output units (4 columns each) per row
@@ -56,7 +198,7 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     const int task = xcd_remap(blockIdx.x, G * S);
     const int g = task / S, s = task - g * S;
     const int KS = K / S;
-    const int NU = KS / (64 * NW);  // 64-k units per wave
+    const int NU = W4 ? 0 : KS / (64 * NW);  // 64-k units per wave (W4: none, this loop is dead and w4_stream runs)
     const int kbase = s * KS + wave * 64 + 8 * (lane >> 4);
 
     const bf16x8* wp[RT];
@@ -74,7 +216,6 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     // (swizzled ds_write_b128, ds_read_b128).  Loads shaped like the MFMA operand (16 rows x 64 B per instruction)
     // reach only ~18 B/clk per CU from L2 against ~50 for whole lines (csrc/microbench/l2_feed.hip): at M = 128 the x
     // re-reads, not the weight stream, set the kernel time.
-    constexpr bool XL = MT >= XL_MIN_MT;
     const bf16x8* xp[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -159,6 +300,8 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
             }
         }
     }
+
+    if constexpr (W4) w4_stream<RT, MT, D, NW, MODE, XL>(a, g, s, KS, lane, wave, smem, acc);
 
     // XL: the reduction slots, inv and the flag alias the other waves' x tiles — wait until every wave's loop is done
     if constexpr (XL) __syncthreads();
@@ -301,12 +444,13 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     }
 }
 
-template <int RT, int MT, int D, int NW, int MODE, bool NORMP>
+template <int RT, int MT, int D, int NW, int MODE, bool NORMP, int WM = kW16, bool XL4 = false>
 void launch_cfg(const PPArgs& a, hipStream_t st) {
     constexpr int UNITS = RT * MT * 64;
     // the reduction slots (+ inv, flag) alias the XL x tiles, which are dead once the main loop ends
-    const int lds = std::max(NW * (UNITS + UNITS / 16) * 16 + 16 * MT * 4 + 16, MT >= XL_MIN_MT ? NW * MT * 2048 : 0);
-    auto kern = skinny_kernel<RT, MT, D, NW, MODE, NORMP>;
+    constexpr int XT = WM == kW4 ? (XL4 ? NW * MT * 4096 : 0) : (MT >= XL_MIN_MT ? NW * MT * 2048 : 0);
+    const int lds = std::max(NW * (UNITS + UNITS / 16) * 16 + 16 * MT * 4 + 16, XT);
+    auto kern = skinny_kernel<RT, MT, D, NW, MODE, NORMP, WM, XL4>;
     static bool attr = false;
     if (!attr) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -348,7 +492,76 @@ bool launch_mode(int cfg, const PPArgs& a, hipStream_t st) {
     }
 }
 
+// W4A16 configs {RT, MT, D (ring depth in 128-k units), NW (K % (128 NW splitk) == 0), XL (x through LDS)}.  A ring
+// stage is 5 RT + 16 MT VGPRs; the budget is 512 registers at NW = 4, 256 at 8, 128 at 16 (one workgroup per CU).
+// Both 8B K (4096 = 128 * 32, 14336 = 128 * 112) divide by 128 * 16, so every config reaches both at splitk 1.
+#define SK4_CONFIGS(X)    \
+    X(0, 4, 1, 4, 4, 0)   \
+    X(1, 4, 1, 4, 4, 1)   \
+    X(2, 4, 1, 3, 8, 0)   \
+    X(3, 2, 1, 4, 8, 0)   \
+    X(4, 2, 1, 4, 8, 1)   \
+    X(5, 2, 1, 2, 16, 0)  \
+    X(6, 1, 1, 3, 16, 0)  \
+    X(7, 4, 2, 3, 4, 1)   \
+    X(8, 2, 2, 3, 8, 1)   \
+    X(9, 4, 2, 2, 8, 1)   \
+    X(10, 4, 4, 2, 4, 1)  \
+    X(11, 2, 4, 2, 8, 1)  \
+    X(12, 2, 4, 2, 4, 1)
+
+template <int MODE, bool NORMP>
+bool launch_mode_w4(int cfg, const PPArgs& a, hipStream_t st) {
+    switch (cfg) {
+#define SK4_CASE(ID, RT_, MT_, D_, NW_, XL_)                                     \
+    case ID:                                                                     \
+        if constexpr (MODE == kSwiglu && RT_ % 2) return false;                  \
+        else {                                                                   \
+            launch_cfg<RT_, MT_, D_, NW_, MODE, NORMP, kW4, XL_ != 0>(a, st);    \
+            return true;                                                         \
+        }
+        SK4_CONFIGS(SK4_CASE)
+#undef SK4_CASE
+        default: return false;
+    }
+}
+
 }  // namespace
+
+int gemm_skinny_w4_rt(int cfg) {
+    switch (cfg) {
+#define SK4_RT(ID, RT_, MT_, D_, NW_, XL_) case ID: return RT_;
+        SK4_CONFIGS(SK4_RT)
+#undef SK4_RT
+        default: return 0;
+    }
+}
+int gemm_skinny_w4_nw(int cfg) {
+    switch (cfg) {
+#define SK4_NW(ID, RT_, MT_, D_, NW_, XL_) case ID: return NW_;
+        SK4_CONFIGS(SK4_NW)
+#undef SK4_NW
+        default: return 0;
+    }
+}
+int gemm_skinny_w4_mt(int cfg) {
+    switch (cfg) {
+#define SK4_MT(ID, RT_, MT_, D_, NW_, XL_) case ID: return MT_;
+        SK4_CONFIGS(SK4_MT)
+#undef SK4_MT
+        default: return 0;
+    }
+}
+
+// W4A16: a.w = q bytes [N, K / 2], a.wexp = e8m0 bytes [N, K / 32]; cfg indexes SK4_CONFIGS
+bool launch_gemm_skinny_w4(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st) {
+    if (a.M == 0) return true;
+    if (a.wexp == nullptr) return false;
+    if (mode == kResid) return normp ? false : launch_mode_w4<kResid, false>(cfg, a, st);
+    if (mode == kSwiglu)
+        return normp ? launch_mode_w4<kSwiglu, true>(cfg, a, st) : launch_mode_w4<kSwiglu, false>(cfg, a, st);
+    return normp ? launch_mode_w4<kPlain, true>(cfg, a, st) : launch_mode_w4<kPlain, false>(cfg, a, st);
+}
 
 int gemm_skinny_rt(int cfg) {
     switch (cfg) {

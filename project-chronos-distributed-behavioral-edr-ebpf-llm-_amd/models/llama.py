@@ -191,10 +191,12 @@ def quantize(w: torch.Tensor) -> QTensor:
 @dataclass
 class Q4Tensor:
     """OCP MXFP4 projection weight (ops.reference.quantize_mxfp4): packed e2m1 ``q`` [N, K / 2] uint8, e8m0 block
-    scales ``e`` [N, K / 32] uint8, and ``w``, the same weights dequantised to bf16 [N, K] (exact).  The W4A16 decode
-    GEMV (csrc/kernels/gemv.hip W4) streams q and e where it measured faster (M = 1, ops/gemm.py W4_MAX_M); every
-    other path — prefill, batched decode, TP / SP / CP, the CPU reference — runs the bf16 kernels on ``w``: the same
-    mathematical product.  Quantised after TP
+    scales ``e`` [N, K / 32] uint8, and ``w``, the same weights dequantised to bf16 [N, K] (exact).  Two kernels stream
+    q and e, each where it measured faster than the bf16 kernel on ``w``: the W4A16 decode GEMV (csrc/kernels/gemv.hip
+    W4) at M = 1 (ops/gemm.py W4_MAX_M) and the W4A16 mode of the skinny MFMA GEMM (csrc/kernels/gemm_skinny.hip) at
+    M = 2-64 on the shapes with a row in ops/gemm_plan.json "w4plans" (jump-forward chunks, 2-64 stream decode;
+    ops/gemm.py W4_SKINNY).  Every other path — prefill, M > 64, unmeasured shapes, TP / SP / CP, the CPU reference —
+    runs the bf16 kernels on ``w``: the same mathematical product.  Quantised after TP
     sharding like QTensor, so a row-parallel shard's MX blocks lie inside its own K-slice.  It has no ``s`` field, so
     ``ops.is_q`` is false for it and everything that asks ``LlamaWeights.fp8`` treats the model as bf16."""
     q: torch.Tensor

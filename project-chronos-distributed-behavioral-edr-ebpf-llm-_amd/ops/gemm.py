@@ -12,6 +12,9 @@ Routing is by measured shape:
   with the kernel, tile config and split-K of the measured plan (``gemm_plan.json``: per (N, K, epilogue) the best
   by M range, from ``scripts/tune_gemm_pp.py`` on one MI355X, random operands, cold weights; plan cfg >= 100 is
   skinny config cfg - 100);
+* MXFP4 weights (a Q4Tensor): the W4A16 GEMV at M = 1, the W4A16 mode of the skinny kernel at M = 2-64 where
+  ``gemm_plan.json`` "w4plans" records it faster than the bf16 route by more than 3 % (``scripts/bench_skinny_w4.py``),
+  the bf16 route on the dequantised copy everywhere else;
 * hipBLASLt (torch.matmul) only where the plan records that the library wins by more than 3 % (the "plain library
   GEMM" rule), or for shapes the kernel does not take (K % 64, N % 4).  CHRONOS_PP=lib|own|auto forces a side.
 """
@@ -64,13 +67,25 @@ SK_BASE = 100
 _SK = {0: (1, 1, 16), 1: (2, 1, 8), 2: (4, 1, 4), 3: (2, 2, 8), 4: (4, 2, 4), 5: (2, 4, 4), 6: (4, 4, 4),
        7: (2, 8, 4), 8: (1, 2, 16), 9: (1, 4, 16), 10: (2, 4, 8), 11: (1, 1, 8)}
 SKINNY_MAX_M = 128
+# W4A16 mode of the same kernel (gemm_skinny.hip SK4_CONFIGS: mxfp4 q / e streamed, bf16 MFMA): own config ids ->
+# (RT, MT, NW); the unit is 128 k, so K % (128 NW split-K) == 0.  M <= 64 (MT <= 4).
+_SK4 = {0: (4, 1, 4), 1: (4, 1, 4), 2: (4, 1, 8), 3: (2, 1, 8), 4: (2, 1, 8), 5: (2, 1, 16), 6: (1, 1, 16),
+        7: (4, 2, 4), 8: (2, 2, 8), 9: (4, 2, 8), 10: (4, 4, 4), 11: (2, 4, 8), 12: (2, 4, 4)}
+W4_SKINNY_MAX_M = 64
+# Which Q4Tensor calls above the fp4 GEMV's M take the W4A16 skinny kernel (env CHRONOS_W4_SKINNY): ``plan`` = the
+# measured rows of gemm_plan.json "w4plans" (a shape with no row runs the bf16 copy), ``off`` = the copy everywhere,
+# ``model`` = the ``_sk4_model`` pick for every valid shape (the tests' way to the kernel on unmeasured shapes, like
+# CHRONOS_PP=own).  Assigning it at run time is allowed: ``w4_plan`` drops the plan cache when it sees a new value.
+W4_SKINNY = os.environ.get("CHRONOS_W4_SKINNY", "plan")
+_w4_skinny_seen = W4_SKINNY
 _plan_cache: dict = {}
 _plan_table: Optional[dict] = None
 _qplan_table: Optional[dict] = None
+_w4plan_table: Optional[dict] = None
 
 
 def _plan_file() -> dict:
-    global _plan_table, _qplan_table
+    global _plan_table, _qplan_table, _w4plan_table
     if _plan_table is None:
         import json
 
@@ -86,6 +101,7 @@ def _plan_file() -> dict:
         key = lambda k: tuple(int(v) for v in k.split(","))  # noqa: E731
         _plan_table = {key(k): rows for k, rows in raw.get("plans", {}).items()}
         _qplan_table = {key(k): rows for k, rows in raw.get("qplans", {}).items()}
+        _w4plan_table = {key(k): rows for k, rows in raw.get("w4plans", {}).items()}
     return _plan_table
 
 
@@ -136,6 +152,62 @@ def _sk_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tup
             if best is None or t < best[0]:
                 best = (t, (SK_BASE + c, sk))
     return best[1] if best else None
+
+
+def _sk4_valid(c: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
+    """The binding's rules for the W4A16 skinny mode (bindings.cpp gemm_skinny with ``we``)."""
+    if c not in _SK4 or sk < 1 or m < 1 or k < 1 or k > (1 << 20):
+        return False
+    rt, mt, nw = _SK4[c]
+    if m > 16 * mt or k % (128 * nw * sk):
+        return False
+    return (rt % 2 == 0 and n % 2 == 0 and (n // 2) % (8 * rt) == 0) if mode == PP_SWIGLU else n % (16 * rt) == 0
+
+
+def _sk4_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tuple[int, int]]:
+    """Cost-model pick of a W4A16 skinny config for a shape without a measured row: the narrowest x tile covering M,
+    split-K only while the grid leaves CUs idle, then the widest W tile and the most waves."""
+    best = None
+    for c, (rt, mt, nw) in _SK4.items():
+        if mt > 1 and m <= 8 * mt:
+            continue
+        groups = (n // 2) // (8 * rt) if mode == PP_SWIGLU else n // (16 * rt)
+        for sk in (1, 2, 4, 7, 8):
+            if not _sk4_valid(c, m, n, k, mode, sk):
+                continue
+            t = (sk > 1 and groups >= cus, -min(groups * sk, cus), sk, -rt, -nw, c)
+            if best is None or t < best[0]:
+                best = (t, (c, sk))
+    return best[1] if best else None
+
+
+def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN) -> Optional[tuple[int, int]]:
+    """(W4 config, split-K) of the W4A16 skinny kernel for a Q4Tensor projection at this shape, or None for the bf16
+    copy.  ``plan``: gemm_plan.json "w4plans", rows [measured M, cfg, split-K] per (N, K, mode) read like "plans"
+    (cfg < 0 = the copy measured faster; no row = never measured = the copy)."""
+    global _w4_skinny_seen
+    if W4_SKINNY != _w4_skinny_seen:
+        _plan_cache.clear()
+        _w4_skinny_seen = W4_SKINNY
+    if not _W4A16_DECODE or W4_SKINNY == "off" or m < 1 or m > W4_SKINNY_MAX_M:
+        return None
+    key = ("w4", m, n, k, mode)
+    hit = _plan_cache.get(key, False)
+    if hit is not False:
+        return hit
+    out = None
+    if W4_SKINNY == "model":
+        out = _sk4_model(m, n, k, mode)
+    else:
+        _plan_file()
+        rows = (_w4plan_table or {}).get((n, k, mode))
+        if rows:
+            pick = next((r for r in rows if m <= r[0]), rows[-1])
+            out = None if pick[1] < 0 else (int(pick[1]), int(pick[2]))
+    if out is not None and not _sk4_valid(out[0], m, n, k, mode, out[1]):
+        out = None
+    _plan_cache[key] = out
+    return out
 
 
 def _pp_valid(cfg: int, n: int, k: int, mode: int, sk: int, m: int = 0) -> bool:
@@ -269,14 +341,18 @@ def gemv_q_ok(m: int, n: int, k: int) -> bool:
 # W4A16 decode: a Q4Tensor (models/llama.py: OCP MXFP4 q / e plus the dequantised bf16 copy w) takes the fp4 GEMV
 # (gemv.hip W4) at its shapes and everything else runs the bf16 kernels on ``.w`` — the same product.  Env
 # CHRONOS_W4A16_DECODE=0 (or this flag) forces ``.w`` everywhere: the A/B switch, and what the tests compare against.
+# Above the GEMV's M, up to 64 rows, a Q4Tensor call takes the W4A16 mode of the skinny MFMA GEMM where ``w4_plan``
+# has a measured row for its shape (W4_SKINNY above).
 _W4A16_DECODE = os.environ.get("CHRONOS_W4A16_DECODE", "1") != "0"
 # Largest M routed to the fp4 kernel (env CHRONOS_W4_MAX_M; the kernel takes up to 4).  Only what wins is routed:
 # on cold 8B weights the fp4 GEMV beats the bf16 GEMV on ``.w`` 1.30-1.75x at M = 1 on all four projections, and at
 # M = 2 and M = 4 it loses on all four, to the bf16 GEMV (0.57-0.90x) and more so to the skinny MFMA GEMM that ``.w``
-# is routed to there (0.29-0.79x) — scripts/bench_gemv_w4.py, profiles/mxfp4/gemv_table.jsonl.  So two-stream decode and
-# jump-forward chunks run on ``.w``; the tests raise this to reach the M = 2..4 instantiations.
+# is routed to there (0.29-0.79x) — scripts/bench_gemv_w4.py, profiles/mxfp4/gemv_table.jsonl.  So the GEMV keeps M = 1
+# only (the tests raise this to reach its M = 2..4 instantiations); two-stream decode and jump-forward chunks go to the
+# W4A16 mode of the skinny MFMA GEMM instead (``w4_plan``), which does beat the routed bf16 kernel there.
 W4_MAX_M = int(os.environ.get("CHRONOS_W4_MAX_M", "1"))
-w4_stats = {"gemv_launches": 0}  # fp4 GEMV launches issued from Python (captured graphs replay them uncounted)
+# fp4 GEMV / W4A16 skinny GEMM launches issued from Python (captured graphs replay them uncounted)
+w4_stats = {"gemv_launches": 0, "skinny_launches": 0}
 
 
 def is_w4(w) -> bool:
@@ -296,6 +372,26 @@ def _w4_route(t: torch.Tensor, m: int, n: int, k: int, mmax: int = 4) -> bool:
         return False
     w4_stats["gemv_launches"] += 1
     return True
+
+
+def _w4_skinny(x, w, mode: int, m: int, resid=None):
+    """The W4A16 skinny launch for a Q4Tensor call the GEMV did not take: (y, partials), or None when ``w4_plan`` has
+    no route (the caller substitutes ``w.w``).  A fusable LazyNorm goes in as the kernel's NORMP prologue."""
+    lazy = isinstance(x, LazyNorm)
+    t = x.s if lazy else x
+    if not t.is_cuda:
+        return None
+    k = t.shape[-1]
+    plan = w4_plan(m, w.shape[0], k, mode)
+    if plan is None:
+        return None
+    from . import _k
+
+    w4_stats["skinny_launches"] += 1
+    if lazy and x.fusable() and mode != PP_RESID:
+        return _k().gemm_skinny(x.s.reshape(-1, k), w.q, mode, plan[0], plan[1], None, x.part, x.eps, w.e)
+    x = LazyNorm.force(x)
+    return _k().gemm_skinny(x.reshape(-1, k), w.q, mode, plan[0], plan[1], resid, None, 1e-5, w.e)
 
 
 def _q_fallback(x, w, swiglu: bool = False) -> torch.Tensor:
@@ -321,6 +417,9 @@ def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOu
             s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
             part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, None, w.e)
             return ResidOut(s, part)
+        hit = _w4_skinny(x, w, PP_RESID, m, resid.reshape(m, -1))
+        if hit is not None:
+            return ResidOut(hit[0].view(resid.shape), hit[1])
         w = w.w
     if is_q(w):
         s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
@@ -390,6 +489,9 @@ def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
             x = LazyNorm.force(x)
             y = _k().gemv(x.reshape(-1, k), w_gu.q, True, None, w_gu.e)
             return y.view(*x.shape[:-1], y.shape[-1])
+        hit = _w4_skinny(x, w_gu, PP_SWIGLU, m)
+        if hit is not None:
+            return hit[0].view(*x.shape[:-1], n // 2)
         w_gu = w_gu.w
     if is_q(w_gu):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
         m, n, k = (x.rows() if isinstance(x, LazyNorm) else x.numel() // x.shape[-1]), w_gu.shape[0], x.shape[-1]
@@ -435,6 +537,9 @@ def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
             x = LazyNorm.force(x)
             y = _k().gemv(x.reshape(-1, k), w.q, False, None, w.e)
             return y.view(*x.shape[:-1], n)
+        hit = _w4_skinny(x, w, PP_PLAIN, m) if out is None else None
+        if hit is not None:
+            return hit[0].view(*x.shape[:-1], n)
         w = w.w
     if is_q(w):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
         from . import _k

@@ -23,12 +23,13 @@ def main():
     ap.add_argument("--jsonl", default="", help="merged table as JSON lines (for profiles/)")
     a = ap.parse_args()
 
-    merged, qmerged, meta = {}, {}, {}
+    merged, qmerged, w4merged, meta = {}, {}, {}, {}
     for path in a.plans:
         with open(path) as fh:
             raw = json.load(fh)
         meta = raw.get("meta", meta)
-        for dst, section in ((merged, "plans"), (qmerged, "qplans")):
+        # "w4plans" (scripts/bench_skinny_w4.py --apply) is carried through a merge
+        for dst, section in ((merged, "plans"), (qmerged, "qplans"), (w4merged, "w4plans")):
             for key, rows in raw.get(section, {}).items():
                 cur = {r[0]: r for r in dst.get(key, [])}
                 cur.update({r[0]: r for r in rows})
@@ -36,7 +37,7 @@ def main():
     if a.plans:
         meta = dict(meta, source="scripts/tune_gemm_pp.py on one MI355X (cold weights); merged by scripts/apply_tune.py")
         with open(a.out, "w") as fh:
-            json.dump({"meta": meta, "plans": merged, "qplans": qmerged}, fh, indent=1)
+            json.dump({"meta": meta, "plans": merged, "qplans": qmerged, "w4plans": w4merged}, fh, indent=1)
         print(f"wrote {a.out}: {len(merged)} bf16 shapes, {len(qmerged)} fp8 shapes")
 
     recs = {}

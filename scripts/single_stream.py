@@ -5,7 +5,12 @@ prefill the kill-chain prompt, decode the schema-constrained verdict, parse it. 
 per-token decode time; ``--ab`` runs the fused decode path (norm-in-GEMV, fused QKV+RoPE, decode gate) and the unfused
 one on two engines in ONE process, interleaved (cdna_hip_programming.md §5.4 rule 24).
 
+``--streams N`` (N > 1) keeps N chains in flight instead, closed loop: every finished verdict is replaced by the next
+chain until ``--chains`` are done — the few-stream regime (decode batches of up to N rows, prefills joining running
+decodes).  It reports verdicts/s, generated tokens/s and the per-chain latency; one variant per process.
+
   python scripts/single_stream.py --chains 16 [--ab] [--out gpurun_out/single.json]
+  python scripts/single_stream.py --chains 64 --streams 4 --weights mxfp4
 """
 import argparse
 import json
@@ -34,8 +39,11 @@ def main():
     ap.add_argument("--knob-ab", default=None,
                     help="';'-separated knob sets ('name=v,name=v'), one fused engine captured under each, interleaved")
     ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16")
+    ap.add_argument("--streams", type=int, default=1, help="chains in flight (closed loop); 1 = one blocking chain")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.streams < 1 or (a.streams > 1 and (a.ab or a.knob_ab)):
+        ap.error("--streams N > 1 runs one variant (no --ab / --knob-ab)")
 
     import torch
 
@@ -47,7 +55,10 @@ def main():
     from chronos import ops
 
     ops.load()
-    prompts = [build_prompt(c.history) for c in synthetic_chains(a.chains + 1, seed=7)]
+    # closed loop: a.streams more chains, run before the clock starts so that the decode graphs of every bucket up to
+    # N rows are captured outside the timed region
+    extra = a.streams if a.streams > 1 else 0
+    prompts = [build_prompt(c.history) for c in synthetic_chains(a.chains + 1 + extra, seed=7)]
     variants = list(VARIANTS) if a.ab else [a.only]
     knobsets = {}
     if a.knob_ab:
@@ -68,7 +79,8 @@ def main():
                 torch.ops.chronos.set_knob(k, v)  # read when this engine's decode graph is captured
         llama._FUSE_NORM = fuse
         burst = knobsets.get(name, {}).get("py_burst", a.burst)
-        eng = Engine(EngineConfig(model=a.model, device="cuda", max_slots=8, max_model_len=512, decode_burst=burst,
+        eng = Engine(EngineConfig(model=a.model, device="cuda", max_slots=max(8, a.streams), max_model_len=512,
+                                  decode_burst=burst,
                                   small_burst=knobsets.get(name, {}).get("py_small_burst", 0),
                                   decode_gate=gate, seed=0, async_harvest=a.async_harvest, weight_dtype=a.weights,
                                   jump_forward=bool(knobsets.get(name, {}).get("py_jump", 1))))
@@ -86,6 +98,8 @@ def main():
         eng.stats.clear()
     from chronos.ops import gemm
 
+    if a.streams > 1:
+        return closed_loop(a, engines[variants[0]][0], prompts[1:], gemm)
     gemv_m0 = gemm.GEMV_MAX_M
     for p in prompts[1:]:
         for name, (eng, fuse) in engines.items():
@@ -113,6 +127,46 @@ def main():
                          jump_host_ms_per_chain=round(1e3 * engines[name][0].phase_s["jump"] / len(rows), 2),
                          bursts_per_chain=round(sum(v for k, v in engines[name][0].stats.items()
                                                     if k.startswith("bursts@")) / len(rows), 2))
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def closed_loop(a, eng, prompts, gemm):
+    """``a.streams`` chains in flight until every prompt has its verdict."""
+    import torch
+
+    from chronos.sensor.prompt import VERDICT_SCHEMA
+
+    warm, pending = list(prompts[:a.streams]), list(prompts[a.streams:])
+    for p in warm:  # N chains together, untimed: graph captures for the 2..N row buckets
+        eng.submit(p, fmt=VERDICT_SCHEMA, num_predict=a.num_predict)
+    eng.run_until_idle()
+    eng.stats.clear()
+    w4_0 = dict(gemm.w4_stats)
+    done = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(min(a.streams, len(pending))):
+        eng.submit(pending.pop(0), fmt=VERDICT_SCHEMA, num_predict=a.num_predict)
+    while eng.has_work():
+        for r in eng.step():
+            done.append(r)
+            if pending:
+                eng.submit(pending.pop(0), fmt=VERDICT_SCHEMA, num_predict=a.num_predict)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    for r in done:
+        assert r.error is None, r.error
+        json.loads(r.text)
+    lat = sorted(r.t_done - r.t_submit for r in done)
+    toks = sum(len(r.out_ids) for r in done)
+    out = dict(streams=a.streams, weights=a.weights, w4_skinny=gemm.W4_SKINNY, chains=len(done), wall_s=round(wall, 3),
+               verdicts_per_s=round(len(done) / wall, 2), tokens_per_s=round(toks / wall, 1),
+               p50_ms=round(1e3 * statistics.median(lat), 2), p90_ms=round(1e3 * lat[int(0.9 * (len(lat) - 1))], 2),
+               mean_tokens=round(toks / len(done), 1), jumps_per_chain=round(eng.stats["jumps"] / len(done), 2),
+               w4_launches={k: v - w4_0.get(k, 0) for k, v in gemm.w4_stats.items()})
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
