@@ -50,6 +50,7 @@ void launch_apply_penalties(void*, bool, int64_t, int, const int32_t*, int, int,
 void launch_truncate_logits(void*, bool, int64_t, const int32_t*, int, int, const int16_t*, const int16_t*, int,
                             const int32_t*, const int32_t*, const float*, const float*, const float*, hipStream_t);
 void launch_gemv(const uint16_t*, int, int, const uint16_t*, int, uint16_t*, bool, hipStream_t);
+void launch_w4_expand(const uint8_t*, const uint8_t*, uint16_t*, int64_t, hipStream_t);
 void attn_init();
 void launch_gemm(const uint16_t*, const uint16_t*, uint16_t*, int, int, int, bool, int, hipStream_t);
 void* ar_create(int, int, int64_t);
@@ -581,6 +582,27 @@ Tensor gemv(const Tensor& x, const Tensor& w, bool swiglu, const c10::optional<T
     return y;
 }
 
+// MXFP4 -> bf16 expansion of a projection weight (csrc/kernels/w4_expand.hip): q uint8 [N, K / 2] packed e2m1, e uint8
+// [N, K / 32] e8m0 block scales, out a bf16 buffer of at least N K elements whose first N K become the contiguous
+// [N, K] dequantisation (the packed-only weight mode's scratch).  Honours the decode gate.
+void w4_expand(const Tensor& q, const Tensor& e, const Tensor& out) {
+    chk_gpu(q, "q");
+    chk_gpu(e, "e");
+    chk_bf16(out, "out");
+    CHK(q.scalar_type() == at::kByte && e.scalar_type() == at::kByte, "w4_expand: q and e must be uint8");
+    CHK(q.device() == e.device() && q.device() == out.device(), "w4_expand: q, e and out must be on one device");
+    CHK(q.dim() == 2 && e.dim() == 2 && q.size(0) >= 1 && q.size(1) >= 16, "w4_expand: q [N, K / 2], e [N, K / 32]");
+    const int64_t N = q.size(0), K = q.size(1) * 2;
+    CHK(K % 32 == 0, "w4_expand: K % 32 == 0 (whole MX blocks)");
+    CHK(e.size(0) == N && e.size(1) == K / 32, "w4_expand: e must be [N, K / 32] for q [N, K / 2]");
+    CHK(N <= (int64_t(1) << 40) / K, "w4_expand: N K too large");
+    CHK(out.numel() >= N * K, "w4_expand: out holds fewer than N K elements");
+    CHK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, "w4_expand: out must be 16-byte aligned");
+    CHK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 4 == 0, "w4_expand: q must be 4-byte aligned");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
+    chronos::launch_w4_expand(q.data_ptr<uint8_t>(), e.data_ptr<uint8_t>(), bfm(out), N * K, cur_stream());
+}
+
 // Decode gate: state = the engine's slot-state vector (int32, >= n rows); n in [1, 8] arms it for the launches that
 // follow, n = 0 disarms.  Only decode steps of a small bucket arm it (a prefill or a large bucket never does).
 void set_decode_gate(const c10::optional<Tensor>& state, int64_t n) {
@@ -1050,6 +1072,7 @@ TORCH_LIBRARY(chronos, m) {
     m.def("qkv_rope(Tensor x, Tensor? part, float eps, Tensor w, Tensor pos, Tensor tok_seq, "
           "Tensor block_table, Tensor cos_sin, Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, int hq, "
           "int hkv, float k_scale=1.0, float v_scale=1.0, Tensor? ws=None, Tensor? we=None) -> ()");
+    m.def("w4_expand(Tensor q, Tensor e, Tensor(a!) out) -> ()");
     m.def("set_decode_gate(Tensor? state, int n) -> ()", &set_decode_gate);
     m.def("attn_init() -> ()", [] { chronos::attn_init(); });
     m.def("quant_rows(Tensor x, Tensor(a!)? resid, Tensor? w, float eps, int mode) -> (Tensor, Tensor)");
@@ -1096,6 +1119,7 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("gemm", &gemm);
     m.impl("gemm_pp", &gemm_pp);
     m.impl("gemm_skinny", &gemm_skinny);
+    m.impl("w4_expand", &w4_expand);
     m.impl("gemv_resid", &gemv_resid);
     m.impl("gemv_normp", &gemv_normp);
     m.impl("qkv_rope", &qkv_rope);

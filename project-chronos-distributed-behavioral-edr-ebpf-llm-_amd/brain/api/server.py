@@ -144,7 +144,9 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
 
     def _model_entry():
         info = backend.info() if hasattr(backend, "info") else {}
-        quant = {"bf16": "BF16", "fp8": "FP8", "mxfp4": "MXFP4"}[getattr(backend, "weight_dtype", "bf16")]
+        # (packed-only MXFP4 is the same numbers as "mxfp4": one quantization level)
+        quant = {"bf16": "BF16", "fp8": "FP8", "mxfp4": "MXFP4",
+                 "mxfp4-packed": "MXFP4"}[getattr(backend, "weight_dtype", "bf16")]
         return {"name": f"{model_name}:latest", "model": f"{model_name}:latest", "modified_at": now_iso(),
                 "size": int(info.get("params", 0)) * 2, "digest": "chronos-random-init",
                 "details": {"format": "safetensors", "family": "llama", "families": ["llama"],
@@ -157,6 +159,8 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
         e = _model_entry()
         e["expires_at"] = "2999-01-01T00:00:00Z"  # weights stay resident (no keep_alive unload, quirk X8)
         e["size_vram"] = e["size"]
+        if getattr(backend, "weight_dtype", "bf16") == "mxfp4-packed" and hasattr(backend, "resident_bytes"):
+            e["size_vram"] = int(backend.resident_bytes)  # what the mode is for: q / e + bf16 rest + the scratch
         return web.json_response({"models": [e]})
 
     async def show(request):
@@ -255,9 +259,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--request-timeout", type=float, default=0.0,
                     help="seconds; a slower generation answers 504 and is cancelled in the engine (0 = none)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
-    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
-                    help="projection weights: bf16, fp8 (W8A8 e4m3) or mxfp4 (OCP MXFP4 for the low-batch decode GEMV, "
-                         "with a resident bf16 copy for every other kernel)")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4", "mxfp4-packed"], default="bf16",
+                    help="projection weights: bf16, fp8 (W8A8 e4m3), mxfp4 (OCP MXFP4 for the low-batch decode GEMV, "
+                         "with a resident bf16 copy for every other kernel) or mxfp4-packed (the same numbers without "
+                         "the copy: 4.25 bits per weight resident, expanded into one scratch in front of the bf16 GEMMs)")
     ap.add_argument("--max-logprobs", type=int, default=20,
                     help="most top_logprobs a request may ask for (0-20); 0 = logprobs are not offered")
     ap.add_argument("--penalty-window", type=int, default=64,

@@ -51,6 +51,12 @@ class EngineService:
     def weight_dtype(self) -> str:
         return self.engine.cfg.weight_dtype
 
+    @property
+    def resident_bytes(self) -> int:
+        """Weight bytes resident on the device, the packed-only MXFP4 mode's expansion scratch included."""
+        w = self.engine.model.w
+        return w.nbytes() + w.scratch_nbytes()
+
     @classmethod
     def from_config(cls, cfg: EngineConfig, model_name: str = "llama3") -> "EngineService":
         return cls(Engine(cfg), model_name)

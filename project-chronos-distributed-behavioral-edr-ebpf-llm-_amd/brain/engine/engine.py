@@ -92,7 +92,8 @@ class EngineConfig:
     kv_dtype: str = "bf16"         # "bf16" or "fp8" (OCP e4m3fn, per-layer scale: half the KV bytes, 2x tokens/GPU)
     # "bf16"; "fp8": W8A8 e4m3 projections on the block-scaled MFMA (csrc/kernels/fp8.hip); "mxfp4": OCP MXFP4
     # projections for the W4A16 single-stream decode GEMV (csrc/kernels/gemv.hip W4) plus a resident bf16 copy for every
-    # other kernel — a latency mode: bf16 + ~0.27 of it again in memory
+    # other kernel — a latency mode: bf16 + ~0.27 of it again in memory; "mxfp4-packed": the same numbers without the
+    # copy (0.27 of bf16 + one scratch of the largest projection, csrc/kernels/w4_expand.hip), the freed HBM becomes KV
     weight_dtype: str = "bf16"
     kv_scale: float = 1.0          # fp8 KV scale (stored = value / scale)
     prefill_nqt: int = 8           # 8 = flash prefill kernel (128 query rows / workgroup); 1-2 = split-K kernel

@@ -198,25 +198,36 @@ class Q4Tensor:
     ops/gemm.py W4_SKINNY).  Every other path — prefill, M > 64, unmeasured shapes, TP / SP / CP, the CPU reference —
     runs the bf16 kernels on ``w``: the same mathematical product.  Quantised after TP
     sharding like QTensor, so a row-parallel shard's MX blocks lie inside its own K-slice.  It has no ``s`` field, so
-    ``ops.is_q`` is false for it and everything that asks ``LlamaWeights.fp8`` treats the model as bf16."""
+    ``ops.is_q`` is false for it and everything that asks ``LlamaWeights.fp8`` treats the model as bf16.
+
+    Packed-only residency (``weight_dtype="mxfp4-packed"``): ``w`` is None and only q and e stay resident, 4.25 bits
+    per weight.  The W4A16 kernels run as above, and at M <= 64 on every shape the skinny kernel accepts (there is no
+    free copy to prefer, ops/gemm.py ``w4_plan``); every other path gets ``w`` rebuilt bit for bit by the expansion
+    kernel (csrc/kernels/w4_expand.hip) into ``scratch``, the model's one bf16 buffer of the largest projection's size
+    (``ops.w4_dense``), right before the bf16 kernel that reads it — the same logits as copy mode."""
     q: torch.Tensor
     e: torch.Tensor
-    w: torch.Tensor
+    w: Optional[torch.Tensor] = None
+    scratch: Optional["ops.W4Scratch"] = None  # packed-only: the model's shared expansion buffer (LlamaWeights owns it)
 
     @property
     def shape(self):
-        return self.w.shape
+        return torch.Size((self.q.shape[0], self.q.shape[1] * 2))
 
     def numel(self) -> int:
-        return self.w.numel()
+        return self.q.numel() * 2
 
     def nbytes(self) -> int:
-        return self.q.numel() + self.e.numel() + 2 * self.w.numel()
+        """Resident bytes (the shared scratch is counted once, by LlamaWeights.scratch_nbytes)."""
+        return self.q.numel() + self.e.numel() + (2 * self.w.numel() if self.w is not None else 0)
 
 
-def quantize_mxfp4(w: torch.Tensor) -> Q4Tensor:
+def quantize_mxfp4(w: torch.Tensor, keep_copy: bool = True) -> Q4Tensor:
     q, e = ops.reference.quantize_mxfp4(w)
-    return Q4Tensor(q, e, ops.reference.dequantize_mxfp4(q, e))
+    return Q4Tensor(q, e, ops.reference.dequantize_mxfp4(q, e) if keep_copy else None)
+
+
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4", "mxfp4-packed")
 
 
 @dataclass
@@ -239,6 +250,21 @@ class LlamaWeights:
     # RMSNorm weights folded into the following projections (W' = W diag(w), norms stored as ones): what the decode
     # GEMV's folded-norm prologue (csrc/kernels/gemv.hip NORMP) relies on
     norms_folded: bool = False
+    # packed-only MXFP4 (Q4Tensor.w is None) on a GPU: the one bf16 expansion buffer all projections share
+    scratch: Optional["ops.W4Scratch"] = None
+
+    def attach_scratch(self) -> None:
+        """Packed-only MXFP4 on a GPU: allocate the expansion scratch (the largest projection's N K bf16 elements, at a
+        fixed address so captured graphs replay the expansion) and hand it to every Q4Tensor.  No-op otherwise."""
+        q4 = [t for l in self.layers for t in (l.wqkv, l.wo, l.w_gu, l.w_down) if isinstance(t, Q4Tensor)]
+        if not q4 or q4[0].w is not None or not q4[0].q.is_cuda or self.scratch is not None:
+            return
+        self.scratch = ops.W4Scratch(max(t.numel() for t in q4), q4[0].q.device)
+        for t in q4:
+            t.scratch = self.scratch
+
+    def scratch_nbytes(self) -> int:
+        return 0 if self.scratch is None else 2 * self.scratch.buf.numel()
 
     def nbytes(self) -> int:
         n = 2 * (self.embed.numel() + self.norm.numel() + (0 if self.lm_head is self.embed else self.lm_head.numel()))
@@ -283,8 +309,8 @@ def fold_norm(wt: torch.Tensor, nw: torch.Tensor) -> torch.Tensor:
 def assemble_layer(cfg: LlamaConfig, tp: TPContext, full: dict, device, dtype=torch.bfloat16,
                    weight_dtype: str = "bf16", fold_norms: bool = True) -> LayerWeights:
     """Full (unsharded) HF-named tensors of one layer -> this rank's fused shard (projections quantised to
-    per-channel e4m3 when ``weight_dtype == "fp8"``, to MXFP4 with a resident bf16 copy when ``"mxfp4"``; norms stay
-    bf16).  ``fold_norms``: the input-norm weights are
+    per-channel e4m3 when ``weight_dtype == "fp8"``, to MXFP4 with a resident bf16 copy when ``"mxfp4"``, to MXFP4
+    without one when ``"mxfp4-packed"``; norms stay bf16).  ``fold_norms``: the input-norm weights are
     folded into QKV / gate_up (before quantisation) and stored as ones."""
     if fold_norms:
         full = dict(full)
@@ -313,10 +339,12 @@ def assemble_layer(cfg: LlamaConfig, tp: TPContext, full: dict, device, dtype=to
         pj = lambda t: quantize(cv(t))  # noqa: E731
     elif weight_dtype == "mxfp4":
         pj = lambda t: quantize_mxfp4(cv(t))  # noqa: E731
+    elif weight_dtype == "mxfp4-packed":  # q / e only: a projection's bf16 form dies with this call
+        pj = lambda t: quantize_mxfp4(cv(t), keep_copy=False)  # noqa: E731
     elif weight_dtype == "bf16":
         pj = cv
     else:
-        raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
+        raise ValueError(f"weight_dtype must be 'bf16', 'fp8', 'mxfp4' or 'mxfp4-packed', got {weight_dtype!r}")
     return LayerWeights(cv(full["attn_norm"]), pj(wqkv), pj(wo), cv(full["mlp_norm"]), pj(w_gu), pj(w_down))
 
 
@@ -906,13 +934,21 @@ def build_model(preset: str | LlamaConfig = "tiny", device="cpu", tp: TPContext 
                 weight_dtype: str = "bf16") -> LlamaModel:
     """``weight_dtype="fp8"``: projections as per-channel e4m3 + W8A8 fp8 MFMA GEMMs (embedding, norms, LM head, attention
     and the KV cache keep their own dtypes).  ``"mxfp4"``: projections as OCP MXFP4 for the W4A16 decode GEMV plus their
-    bf16 dequantisation for every other kernel (Q4Tensor)."""
+    bf16 dequantisation for every other kernel (Q4Tensor).  ``"mxfp4-packed"``: the same model without the resident
+    dequantisation — q / e only, plus one scratch of the largest projection's size that the expansion kernel fills in
+    front of every bf16 kernel (same logits); on a GPU the allocator's cached blocks go back to the driver afterwards,
+    so whoever sizes a KV pool from free memory sees what the mode saves."""
     tp = tp or TPContext.single()
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
     if checkpoint:
         cfg, w = load_checkpoint(checkpoint, tp, device, weight_dtype)
     else:
         cfg = preset if isinstance(preset, LlamaConfig) else get_config(preset)
         w = random_weights(cfg, tp, device, seed, weight_dtype=weight_dtype)
+    if weight_dtype == "mxfp4-packed" and torch.device(device).type == "cuda":
+        torch.cuda.empty_cache()  # the load's transient bf16 projections
+        w.attach_scratch()
     return LlamaModel(cfg, w, tp, device, max_position)
 
 

@@ -4,7 +4,8 @@ There is no silent fallback on a GPU: a CUDA/HIP tensor always goes to ``torch.o
 extension (``_C*.so``, built by :mod:`chronos.native`) cannot be built or loaded the op raises.  CPU tensors (tests,
 the gloo-backed distributed tests, the CPU plumbing config) take :mod:`.reference`.
 
-Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties,truncate}.hip.
+Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties,truncate,w4_expand}.hip (SURVEY.md §2.3
+K1-K14).
 """
 from __future__ import annotations
 
@@ -14,8 +15,8 @@ import os
 import torch
 
 from . import reference as ref
-from .gemm import (LazyNorm, ResidOut, gate_up_silu, gemv_ok, gemv_q_ok, gemv_resid, gemv_w4_ok, is_q,  # noqa: F401
-                   is_w4, linear, resid_ok)
+from .gemm import (LazyNorm, ResidOut, W4Scratch, gate_up_silu, gemv_ok, gemv_q_ok, gemv_resid,  # noqa: F401
+                   gemv_w4_ok, is_q, is_w4, linear, resid_ok, w4_dense, w4_expand)
 
 _loaded = False
 
@@ -194,7 +195,9 @@ def qkv_rope(x, w_qkv, pos, tok_seq, block_table, cos_sin, q_out, k_cache, v_cac
             _k().qkv_rope(t.reshape(m, k), x.part if lazy else None, x.eps if lazy else 0.0, w_qkv.q, pos, tok_seq,
                           block_table, cos_sin, q_out, k_cache, v_cache, hq, hkv, k_scale, v_scale, None, w_qkv.e)
             return True
-        w_qkv = w_qkv.w
+        if not (t.is_cuda and m <= 2 and gemv_ok(m, n, k)):  # (before w4_dense: no expansion for a call not made)
+            return False
+        w_qkv = w4_dense(w_qkv)
     fp8w = is_q(w_qkv)  # fp8 weights: the W8A16 GEMV (e4m3 bytes + per-row scales)
     if not (t.is_cuda and m <= 2 and (gemv_q_ok(m, n, k) if fp8w else gemv_ok(m, n, k))):
         return False

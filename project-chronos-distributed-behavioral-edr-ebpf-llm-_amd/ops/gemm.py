@@ -14,7 +14,9 @@ Routing is by measured shape:
   skinny config cfg - 100);
 * MXFP4 weights (a Q4Tensor): the W4A16 GEMV at M = 1, the W4A16 mode of the skinny kernel at M = 2-64 where
   ``gemm_plan.json`` "w4plans" records it faster than the bf16 route by more than 3 % (``scripts/bench_skinny_w4.py``),
-  the bf16 route on the dequantised copy everywhere else;
+  the bf16 route on the dequantised copy everywhere else.  A packed-only Q4Tensor (no copy) takes the skinny kernel
+  on every M <= 64 shape it accepts, and everywhere else the bf16 route on a scratch that one ``w4_expand`` launch
+  (csrc/kernels/w4_expand.hip) fills in front of the GEMM (``w4_dense``): the same bits as the copy;
 * hipBLASLt (torch.matmul) only where the plan records that the library wins by more than 3 % (the "plain library
   GEMM" rule), or for shapes the kernel does not take (K % 64, N % 4).  CHRONOS_PP=lib|own|auto forces a side.
 """
@@ -181,17 +183,22 @@ def _sk4_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tu
     return best[1] if best else None
 
 
-def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN) -> Optional[tuple[int, int]]:
+def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) -> Optional[tuple[int, int]]:
     """(W4 config, split-K) of the W4A16 skinny kernel for a Q4Tensor projection at this shape, or None for the bf16
     copy.  ``plan``: gemm_plan.json "w4plans", rows [measured M, cfg, split-K] per (N, K, mode) read like "plans"
-    (cfg < 0 = the copy measured faster; no row = never measured = the copy)."""
+    (cfg < 0 = the copy measured faster; no row = never measured = the copy).
+
+    ``packed`` (a Q4Tensor without the copy): the alternative is no longer a free resident copy but an expansion —
+    a full write and re-read of the weight matrix in front of the bf16 kernel — so every shape the kernel accepts takes
+    it: the plan's winning row where there is one, the ``_sk4_model`` pick for a shape without a row and for a row the
+    copy won (by at most 13 %, QKV / gate_up at M = 40-64; scripts/bench_w4_expand.py measures those points)."""
     global _w4_skinny_seen
     if W4_SKINNY != _w4_skinny_seen:
         _plan_cache.clear()
         _w4_skinny_seen = W4_SKINNY
     if not _W4A16_DECODE or W4_SKINNY == "off" or m < 1 or m > W4_SKINNY_MAX_M:
         return None
-    key = ("w4", m, n, k, mode)
+    key = ("w4p" if packed else "w4", m, n, k, mode)
     hit = _plan_cache.get(key, False)
     if hit is not False:
         return hit
@@ -204,6 +211,8 @@ def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN) -> Optional[tuple[int,
         if rows:
             pick = next((r for r in rows if m <= r[0]), rows[-1])
             out = None if pick[1] < 0 else (int(pick[1]), int(pick[2]))
+        if packed and (out is None or not _sk4_valid(out[0], m, n, k, mode, out[1])):
+            out = _sk4_model(m, n, k, mode)
     if out is not None and not _sk4_valid(out[0], m, n, k, mode, out[1]):
         out = None
     _plan_cache[key] = out
@@ -340,7 +349,9 @@ def gemv_q_ok(m: int, n: int, k: int) -> bool:
 
 # W4A16 decode: a Q4Tensor (models/llama.py: OCP MXFP4 q / e plus the dequantised bf16 copy w) takes the fp4 GEMV
 # (gemv.hip W4) at its shapes and everything else runs the bf16 kernels on ``.w`` — the same product.  Env
-# CHRONOS_W4A16_DECODE=0 (or this flag) forces ``.w`` everywhere: the A/B switch, and what the tests compare against.
+# CHRONOS_W4A16_DECODE=0 (or this flag) forces ``.w`` everywhere: the A/B switch, and what the tests compare against
+# (a packed-only Q4Tensor has no ``.w``: there ``w4_dense`` expands it into the model's scratch, so the switch means
+# "expand everywhere" and gives copy mode's bits).
 # Above the GEMV's M, up to 64 rows, a Q4Tensor call takes the W4A16 mode of the skinny MFMA GEMM where ``w4_plan``
 # has a measured row for its shape (W4_SKINNY above).
 _W4A16_DECODE = os.environ.get("CHRONOS_W4A16_DECODE", "1") != "0"
@@ -352,12 +363,76 @@ _W4A16_DECODE = os.environ.get("CHRONOS_W4A16_DECODE", "1") != "0"
 # W4A16 mode of the skinny MFMA GEMM instead (``w4_plan``), which does beat the routed bf16 kernel there.
 W4_MAX_M = int(os.environ.get("CHRONOS_W4_MAX_M", "1"))
 # fp4 GEMV / W4A16 skinny GEMM launches issued from Python (captured graphs replay them uncounted)
-w4_stats = {"gemv_launches": 0, "skinny_launches": 0}
+w4_stats = {"gemv_launches": 0, "skinny_launches": 0, "expand_launches": 0}
 
 
 def is_w4(w) -> bool:
-    """An MXFP4 projection weight (models/llama.py Q4Tensor: packed e2m1 ``q``, e8m0 ``e``, bf16 copy ``w``)."""
+    """An MXFP4 projection weight (models/llama.py Q4Tensor: packed e2m1 ``q``, e8m0 ``e``, bf16 copy ``w`` — None in
+    the packed-only mode)."""
     return not isinstance(w, torch.Tensor) and hasattr(w, "q") and hasattr(w, "e") and hasattr(w, "w")
+
+
+class W4Scratch:
+    """The packed-only MXFP4 model's one bf16 expansion buffer (``LlamaWeights.scratch``), sized to its largest
+    projection.  Every ``w4_dense`` call overwrites it, so its contents live from one expansion to the GEMM issued
+    right after it and reuse is safe under stream order only: ``acquire`` remembers the stream of the last use and,
+    when the next use comes on another stream, makes that stream wait for everything issued so far on the previous one
+    (the previous GEMM included).  The model issues every projection on the current stream — the TP overlap paths put
+    only the all-reduces on a side stream — so in practice the wait never fires.  Entering or leaving a graph capture
+    changes the stream too, but both sides of that boundary are ordered by the capture itself (it begins after the
+    device is idle and a replay is one launch on the stream that issues it), and an event wait across it would be an
+    illegal cross-capture dependency: no wait there."""
+
+    def __init__(self, numel: int, device):
+        self.buf = torch.empty(int(numel), dtype=torch.bfloat16, device=device)
+        self._stream = None
+        self._capturing = False
+
+    def acquire(self) -> torch.Tensor:
+        cur = torch.cuda.current_stream(self.buf.device)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._stream is not None and cur != self._stream and capturing == self._capturing:
+            cur.wait_stream(self._stream)
+        self._stream, self._capturing = cur, capturing
+        return self.buf
+
+
+def w4_expand(q: torch.Tensor, e: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [N, K] of MXFP4 q [N, K / 2] / e [N, K / 32], bit-equal to ``reference.dequantize_mxfp4``: one launch of
+    csrc/kernels/w4_expand.hip into ``out`` (any contiguous bf16 buffer of >= N K elements, 16-B aligned; its first N K
+    elements are returned as the matrix) or into a new tensor.  CPU tensors take the reference."""
+    n, k = q.shape[0], q.shape[1] * 2
+    if not q.is_cuda:
+        from . import reference
+
+        w = reference.dequantize_mxfp4(q, e)
+        if out is None:
+            return w
+        dst = out.view(-1)[:n * k].view(n, k)
+        dst.copy_(w)
+        return dst
+    from . import _k
+
+    if out is None:
+        out = torch.empty(n, k, dtype=torch.bfloat16, device=q.device)
+    _k().w4_expand(q, e, out)
+    return out.view(-1)[:n * k].view(n, k)
+
+
+def w4_dense(w) -> torch.Tensor:
+    """The bf16 [N, K] form of a Q4Tensor for a bf16 kernel: the resident copy where there is one (no launch, as
+    before), else the model's scratch after one expansion launch on the current stream — valid until the next
+    ``w4_dense`` call, so the caller's GEMM goes out right after it.  CPU: the reference dequantisation."""
+    if w.w is not None:
+        return w.w
+    if not w.q.is_cuda:
+        from . import reference
+
+        return reference.dequantize_mxfp4(w.q, w.e)
+    if w.scratch is None:
+        raise RuntimeError("packed-only Q4Tensor without an expansion scratch (LlamaWeights.attach_scratch)")
+    w4_stats["expand_launches"] += 1
+    return w4_expand(w.q, w.e, w.scratch.acquire())
 
 
 def gemv_w4_ok(m: int, n: int, k: int) -> bool:
@@ -382,7 +457,7 @@ def _w4_skinny(x, w, mode: int, m: int, resid=None):
     if not t.is_cuda:
         return None
     k = t.shape[-1]
-    plan = w4_plan(m, w.shape[0], k, mode)
+    plan = w4_plan(m, w.shape[0], k, mode, w.w is None)
     if plan is None:
         return None
     from . import _k
@@ -420,7 +495,7 @@ def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOu
         hit = _w4_skinny(x, w, PP_RESID, m, resid.reshape(m, -1))
         if hit is not None:
             return ResidOut(hit[0].view(resid.shape), hit[1])
-        w = w.w
+        w = w4_dense(w)
     if is_q(w):
         s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
         part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, w.s)
@@ -492,7 +567,7 @@ def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
         hit = _w4_skinny(x, w_gu, PP_SWIGLU, m)
         if hit is not None:
             return hit[0].view(*x.shape[:-1], n // 2)
-        w_gu = w_gu.w
+        w_gu = w4_dense(w_gu)
     if is_q(w_gu):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
         m, n, k = (x.rows() if isinstance(x, LazyNorm) else x.numel() // x.shape[-1]), w_gu.shape[0], x.shape[-1]
         if isinstance(x, LazyNorm) and x.fusable() and m <= 2 and gemv_q_ok(m, n, k):
@@ -540,7 +615,7 @@ def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
         hit = _w4_skinny(x, w, PP_PLAIN, m) if out is None else None
         if hit is not None:
             return hit[0].view(*x.shape[:-1], n)
-        w = w.w
+        w = w4_dense(w)
     if is_q(w):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
         from . import _k
 

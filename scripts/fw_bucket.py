@@ -46,7 +46,7 @@ def main():
     ap.add_argument("--rows", type=int, default=128)
     ap.add_argument("--ctx", type=int, default=200)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "mxfp4"])
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "mxfp4", "mxfp4-packed"])
     ap.add_argument("--knob", action="append", default=[], help="kernel knob name=value (torch.ops.chronos.set_knob)")
     ap.add_argument("--tp-rank-of", type=int, default=1, help="W > 1: one rank of a W-way TP model, local collectives")
     a = ap.parse_args()
@@ -92,7 +92,9 @@ def main():
     print(json.dumps({"model": a.model, "tp_rank_of": a.tp_rank_of, "weights": a.weights, "rows": n, "ctx": a.ctx,
                       "knobs": a.knob,
                       "ms_per_forward": round(ms, 3),
-                      "weight_GB": round(wbytes / 1e9, 2), "weight_stream_TBps": round(wbytes / ms / 1e9, 2)}))
+                      "weight_GB": round(wbytes / 1e9, 2), "weight_stream_TBps": round(wbytes / ms / 1e9, 2),
+                      "scratch_GB": round(m.w.scratch_nbytes() / 1e9, 3),
+                      "mem_allocated_GB": round(torch.cuda.memory_allocated() / 1e9, 2)}))
 
 
 if __name__ == "__main__":

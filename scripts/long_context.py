@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--model", default="llama3.1-8b")
     ap.add_argument("--tokens", type=int, default=131000)
     ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"])
-    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "mxfp4"],
+    ap.add_argument("--weights", default="bf16", choices=["bf16", "fp8", "mxfp4", "mxfp4-packed"],
                     help="fp8: W8A8 e4m3 projections on the block-scaled MFMA (the config's 'CDNA4 fp8 MFMA')")
     ap.add_argument("--chunk", type=int, default=16384)
     ap.add_argument("--num-predict", type=int, default=64)

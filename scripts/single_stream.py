@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--only", choices=list(VARIANTS), default="fused", help="variant without --ab")
     ap.add_argument("--knob-ab", default=None,
                     help="';'-separated knob sets ('name=v,name=v'), one fused engine captured under each, interleaved")
-    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4", "mxfp4-packed"], default="bf16")
     ap.add_argument("--streams", type=int, default=1, help="chains in flight (closed loop); 1 = one blocking chain")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -126,11 +126,22 @@ def main():
                          jump_tokens_per_chain=round(engines[name][0].stats["jump_tokens"] / len(rows), 2),
                          jump_host_ms_per_chain=round(1e3 * engines[name][0].phase_s["jump"] / len(rows), 2),
                          bursts_per_chain=round(sum(v for k, v in engines[name][0].stats.items()
-                                                    if k.startswith("bursts@")) / len(rows), 2))
+                                                    if k.startswith("bursts@")) / len(rows), 2),
+                         **residency(engines[name][0]))
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
+
+
+def residency(eng):
+    """What a weight mode costs in HBM: the model's resident bytes (the packed-only MXFP4 scratch included), the
+    allocator's total with the KV pool, and the KV blocks the engine sized from what was free."""
+    import torch
+
+    w = eng.model.w
+    return dict(weight_gb=round((w.nbytes() + w.scratch_nbytes()) / 2**30, 3),
+                mem_allocated_gb=round(torch.cuda.memory_allocated() / 2**30, 3), kv_blocks=eng.blocks.num_blocks)
 
 
 def closed_loop(a, eng, prompts, gemm):
@@ -166,7 +177,7 @@ def closed_loop(a, eng, prompts, gemm):
                verdicts_per_s=round(len(done) / wall, 2), tokens_per_s=round(toks / wall, 1),
                p50_ms=round(1e3 * statistics.median(lat), 2), p90_ms=round(1e3 * lat[int(0.9 * (len(lat) - 1))], 2),
                mean_tokens=round(toks / len(done), 1), jumps_per_chain=round(eng.stats["jumps"] / len(done), 2),
-               w4_launches={k: v - w4_0.get(k, 0) for k, v in gemm.w4_stats.items()})
+               w4_launches={k: v - w4_0.get(k, 0) for k, v in gemm.w4_stats.items()}, **residency(eng))
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:
