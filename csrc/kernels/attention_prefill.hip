@@ -926,6 +926,7 @@ __global__ void __launch_bounds__(256, 2) attn_prefill8_kernel(
             const float alpha = __builtin_amdgcn_exp2f(m - mnew);
             m = mnew;
             lsum *= alpha;
+            if constexpr (kMfmaSum) lacc *= alpha;  // the MFMA row sums are rescaled with O (MSUM without FOLD)
 #pragma unroll
             for (int db = 0; db < 4; ++db) o[db] *= alpha;
         }

@@ -116,19 +116,19 @@ class Probe:
         return Probe(**kw)
 
 
-def _store(x: torch.Tensor, fp8: bool) -> torch.Tensor:
-    """Logical f32 cache -> stored bf16 / e4m3 bytes (value / KV_SCALE); the probes must survive it unchanged."""
+def _store(x: torch.Tensor, fp8: bool, scale: float = KV_SCALE) -> torch.Tensor:
+    """Logical f32 cache -> stored bf16 / e4m3 bytes (value / scale); the probes must survive it unchanged."""
     if fp8:
-        b = (x / KV_SCALE).to(torch.float8_e4m3fn)
-        assert torch.equal(b.float() * KV_SCALE, x), "probe value not exact in e4m3"
+        b = (x / scale).to(torch.float8_e4m3fn)
+        assert torch.equal(b.float() * scale, x), "probe value not exact in e4m3"
         return b.view(torch.uint8)
     b = x.to(torch.bfloat16)
     assert torch.equal(b.float(), x), "probe value not exact in bf16"
     return b
 
 
-def _load(x: torch.Tensor, fp8: bool) -> torch.Tensor:
-    return ref.from_fp8_bytes(x, KV_SCALE) if fp8 else x.float()
+def _load(x: torch.Tensor, fp8: bool, scale: float = KV_SCALE) -> torch.Tensor:
+    return ref.from_fp8_bytes(x, scale) if fp8 else x.float()
 
 
 def _q_support(c: int) -> list:
