@@ -213,7 +213,8 @@ __global__ void __launch_bounds__(1024) constrained_sample_kernel(
         if (thr && ord_key(sc) < thr) continue;
         if (temp > 0.f) {
             const uint32_t hsh = mix32(key ^ (uint32_t)v * 0xC2B2AE35U);
-            const float u = ((hsh >> 8) + 0.5f) * (1.f / 16777216.f);
+            // 23 hash bits + 0.5 has 24 significant bits: u is exact in fp32 and 2^-24 <= u <= 1 - 2^-24, never 1
+            const float u = ((hsh >> 9) + 0.5f) * (1.f / 8388608.f);
             sc = sc * invt - __logf(-__logf(u));
         }
         if (sc > best || (sc == best && v < besti)) {

@@ -233,10 +233,49 @@ def topkp_threshold(logits: torch.Tensor, legal: torch.Tensor, top_k: int, top_p
     return thr
 
 
+_M32 = 0xFFFFFFFF
+
+
+def _mul32(x: torch.Tensor, c: int) -> torch.Tensor:
+    """x * c mod 2^32 for int64 x in [0, 2^32): two 16-bit halves of c, so no int64 product overflows."""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def _mix32(x: torch.Tensor) -> torch.Tensor:
+    """csrc/kernels/sampler.hip mix32 on int64 values masked to 32 bits."""
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def sampler_hash(seed, nout, slot, vocab: int) -> torch.Tensor:
+    """The sampler kernel's 32-bit hash of tokens 0..vocab-1 (int64 tensor [..., vocab]): a pure function of (seed,
+    nout, slot, token).  The three enter as ``(uint32_t)`` of an ``int32_t``, so a negative seed wraps; each may be
+    an int or an integer tensor (broadcast against each other)."""
+    s, n, b = (torch.as_tensor(a, dtype=torch.int64) & _M32 for a in (seed, nout, slot))
+    key = _mix32(_mul32(s, 0x9E3779B9) ^ _mul32(n, 0x85EBCA6B) ^ b)
+    return _mix32(key[..., None] ^ _mul32(torch.arange(vocab, dtype=torch.int64), 0xC2B2AE35))
+
+
+def uniform_of_hash(hsh: torch.Tensor) -> torch.Tensor:
+    """fp32 u of a 32-bit hash, as the kernel forms it: the top 23 bits plus a half, times 2^-23.  Every step is
+    exact in fp32 (h + 0.5 has at most 24 significant bits), so 2^-24 <= u <= 1 - 2^-24."""
+    return ((hsh >> 9).to(torch.float32) + 0.5) * (1.0 / 8388608.0)
+
+
+def sampler_uniform(seed, nout, slot, vocab: int) -> torch.Tensor:
+    """The uniform the sampler kernel draws for tokens 0..vocab-1 at (seed, nout, slot): fp32, bit for bit."""
+    return uniform_of_hash(sampler_hash(seed, nout, slot, vocab))
+
+
 def constrained_sample(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, temperature, seed,
                        ids, pos, ctx, nout, out_tokens, topk=None, topp=None, jump=None) -> None:
     """Greedy / Gumbel-max sampling restricted by the token DFA; advances the slot state in place (host loop).
-    A row entering a state flagged in ``jump`` is parked as ``-2 - state``."""
+    A row entering a state flagged in ``jump`` is parked as ``-2 - state``.  Sampled rows draw the kernel's own
+    counter-hash stream (``sampler_uniform``) and score in fp64, so both backends pick the same token for the same
+    (seed, step, slot) unless the two best scores lie within the kernel's fp32 rounding of each other."""
     n = state.numel()
     V = next_tab.shape[1]
     for slot in range(n):
@@ -261,10 +300,8 @@ def constrained_sample(logits, row_of_slot, next_tab, dist, done_state: int, sta
             thr = topkp_threshold(sc, legal, tk, tp)
             legal = legal & (ord_key(sc) >= thr)
         if t > 0:
-            g = torch.Generator(device="cpu")
-            g.manual_seed((int(seed[slot]) if seed is not None else 0) * 1000003 + int(nout[slot]) * 7919 + slot)
-            u = torch.rand(V, generator=g).clamp_(1e-7, 1 - 1e-7).to(sc.device)
-            sc = sc / t - torch.log(-torch.log(u))
+            u = sampler_uniform(int(seed[slot]) if seed is not None else 0, int(nout[slot]), slot, V).to(sc.device)
+            sc = sc.double() / t - torch.log(-torch.log(u.double()))
         sc = sc.masked_fill(~legal, float("-inf"))
         tok = int(torch.argmax(sc))
         ns = int(nx[tok])

@@ -258,7 +258,8 @@ def test_constrained_sample_matches_reference():
     for step in range(45):
         logits = (torch.randn(S, 128256, device=DEV, generator=g) * 3).to(torch.bfloat16)
         ops.constrained_sample(logits, None, bank.next, bank.dist, DONE, st1, r1, temp, seed, *bufs1)
-        # reference on greedy rows only (the Gumbel RNG streams differ by design)
+        # reference on greedy rows only (the sampled rows are checked token by token against the replayed noise
+        # stream in tests/test_sampler_replay_gpu.py)
         greedy = (temp == 0)
         st2g = torch.where(greedy, st2, torch.full_like(st2, -1))
         ref.constrained_sample(logits, None, bank.next, bank.dist, DONE, st2g, r2, temp, seed, *bufs2)
