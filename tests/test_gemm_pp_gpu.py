@@ -1,7 +1,9 @@
 """Numerics of the batched projection GEMM family (csrc/kernels/gemm_pp.hip) against an fp32 PyTorch reference.
 
-Every tile config, split-K, and all three epilogues (plain, SwiGLU, residual + RMSNorm partials) plus the folded-norm
-prologue, at ragged M (partial last tiles) with asymmetric random operands.  Run on an MI355X: ``pytest -m gpu``.
+Tile configs 0-39 and 72-80 (78-80 not in every test; the HB configs 81-94 are in test_gemm_hb_gpu.py), split-K, and
+all three epilogues (plain, SwiGLU, residual + RMSNorm partials) plus the folded-norm prologue, at ragged M (partial
+last tiles) with asymmetric random operands under a max-norm tolerance.  The config-complete sweep, with exact integer
+operands, is tests/test_gemm_probes_gpu.py.  Run on an MI355X: ``pytest -m gpu``.
 """
 import pytest
 import torch
