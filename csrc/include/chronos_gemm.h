@@ -68,4 +68,14 @@ int gemm_skinny_w4_mt(int cfg);
 int gemm_skinny_w4_nw(int cfg);
 bool launch_gemm_skinny_w4(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st);
 
+// mid-M W4A16 family (csrc/kernels/gemm_w4m.hip, any M; routed for 65 <= M <= 512): a.w = packed e2m1 [N, K / 2],
+// a.wexp = e8m0 [N, K / 32], same epilogues; 4 waves, tile = WN W rows x XM x rows, x through an LDS ring of ST
+// 128-k stages; ws holds [tiles * splitk, WN * XM] f32 slabs, cnt one ticket per tile, kResid partials are
+// [M, N / (WN / 2)]; K % (128 * splitk) == 0, N % WN == 0 (swiglu: F % (WN / 2) == 0)
+constexpr int kW4MConfigs = 4;
+int gemm_w4m_wn(int cfg);  // W rows per tile
+int gemm_w4m_xm(int cfg);  // x rows per tile
+int gemm_w4m_st(int cfg);  // ring stages
+bool launch_gemm_w4m(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st);
+
 }  // namespace chronos

@@ -901,6 +901,94 @@ std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t
     return {y, part_out};
 }
 
+// Mid-M W4A16 GEMM (gemm_w4m.hip): x bf16 [M, K], q uint8 [N, K / 2] packed e2m1, e uint8 [N, K / 32] e8m0 (OCP
+// MXFP4); same modes, resid / part_in / eps and outputs as gemm_skinny.  cfg indexes W4M_CONFIGS (tile = WN W rows x XM
+// x rows, any M >= 1), K % (128 * splitk) == 0, N % WN == 0 (swiglu: F % (WN / 2) == 0); the kResid partials are
+// [M, N / (WN / 2)].
+std::tuple<Tensor, Tensor> gemm_w4m(const Tensor& x, const Tensor& q, const Tensor& e, int64_t mode, int64_t cfg,
+                                    int64_t splitk, const c10::optional<Tensor>& resid,
+                                    const c10::optional<Tensor>& part_in, double eps) {
+    chk_bf16(x, "x");
+    chk_gpu(q, "q");
+    chk_gpu(e, "e");
+    CHK(x.dim() >= 1 && x.size(-1) > 0, "gemm_w4m: x must be [M, K]");
+    const int64_t K = x.size(-1), M = x.numel() / K, N = q.size(0);
+    CHK(q.scalar_type() == at::kByte && q.dim() == 2 && K % 32 == 0 && q.size(1) == K / 2,
+        "gemm_w4m: q must be uint8 [N, K / 2]");
+    CHK(e.scalar_type() == at::kByte && e.dim() == 2 && e.size(0) == N && e.size(1) == K / 32,
+        "gemm_w4m: e must be uint8 [N, K / 32]");
+    CHK(q.device() == x.device() && e.device() == x.device(), "gemm_w4m: q / e on x's device");
+    CHK(cfg >= 0 && cfg < chronos::kW4MConfigs, "gemm_w4m: cfg");
+    CHK(mode >= 0 && mode <= 2, "gemm_w4m: mode");
+    const int WN = chronos::gemm_w4m_wn((int)cfg), XM = chronos::gemm_w4m_xm((int)cfg);
+    // x is addressed through a buffer descriptor: 32-bit byte offsets
+    CHK(M >= 1 && K <= (1 << 20) && M * K < (1LL << 30) && N * K < (1LL << 40), "gemm_w4m: size (M K < 2^30)");
+    CHK(splitk >= 1 && K % (128 * splitk) == 0, "gemm_w4m: K % (128 * splitk) == 0");
+    CHK(mode == 1 ? N % 2 == 0 && (N / 2) % (WN / 2) == 0 : N % WN == 0,
+        "gemm_w4m: N % WN (swiglu: F % (WN / 2)) == 0");
+    CHK(mode != 2 || !part_in.has_value(), "gemm_w4m: resid mode has no norm prologue");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+    chronos::PPArgs a{};
+    a.x = bf(x);
+    a.w = reinterpret_cast<const uint16_t*>(q.data_ptr<uint8_t>());
+    a.wexp = e.data_ptr<uint8_t>();
+    a.M = (int)M;
+    a.N = (int)N;
+    a.K = (int)K;
+    a.F = (int)(N / 2);
+    a.splitk = (int)splitk;
+    a.eps = (float)eps;
+    Tensor y = at::empty({M, mode == 1 ? N / 2 : N}, x.options());
+    a.y = bfm(y);
+    Tensor part_out;
+    if (mode == 2) {
+        CHK(resid.has_value(), "gemm_w4m: resid mode needs resid");
+        chk_bf16(*resid, "resid");
+        CHK(resid->numel() == M * N && resid->device() == x.device(), "gemm_w4m: resid must be [M, N] on x's device");
+        a.resid = bf(*resid);
+        part_out = at::empty({M, N / (WN / 2)}, x.options().dtype(at::kFloat));
+        a.part_out = part_out.data_ptr<float>();
+    }
+    if (part_in.has_value()) {
+        chk_gpu(*part_in, "part_in");
+        CHK(part_in->scalar_type() == at::kFloat && part_in->dim() == 2 && part_in->size(0) == M &&
+                part_in->size(1) >= 1 && part_in->device() == x.device(),
+            "gemm_w4m: part_in must be f32 [M, P] on x's device");
+        a.part_in = part_in->data_ptr<float>();
+        a.nparts_in = (int)part_in->size(1);
+    }
+    const int64_t tiles = ((M + XM - 1) / XM) * (mode == 1 ? (N / 2) / (WN / 2) : N / WN);
+    CHK(tiles * splitk < (1LL << 31), "gemm_w4m: grid");
+    Tensor ws;
+    if (splitk > 1) {
+        ws = at::empty({tiles * splitk * WN * XM}, x.options().dtype(at::kFloat));
+        a.ws = ws.data_ptr<float>();
+        a.cnt = split_tickets(x, tiles);
+    }
+    CHK(chronos::launch_gemm_w4m((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()), "gemm_w4m: launch");
+    return {y, part_out};
+}
+
+// [kW4MConfigs, 3] int64 on the CPU: (WN, XM, ST) per config id, so that ops/gemm.py's table can be pinned to the kernel's
+Tensor gemm_w4m_configs() {
+    Tensor t = at::empty({chronos::kW4MConfigs, 3}, at::TensorOptions().dtype(at::kLong));
+    auto acc = t.accessor<int64_t, 2>();
+    for (int c = 0; c < chronos::kW4MConfigs; ++c) {
+        acc[c][0] = chronos::gemm_w4m_wn(c);
+        acc[c][1] = chronos::gemm_w4m_xm(c);
+        acc[c][2] = chronos::gemm_w4m_st(c);
+    }
+    return t;
+}
+
+// The split-K tickets of like's device and the current stream (what the GEMM families' launches use): every launch
+// must leave them at zero.  An empty tensor before the first split-K launch.
+Tensor split_ticket_state(const Tensor& like) {
+    chk_gpu(like, "like");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(like.device());
+    return at::from_blob(split_tickets(like, 1), {1 << 16}, like.options().dtype(at::kInt)).clone();
+}
+
 // ---- W8A8 fp8-e4m3 path (fp8.hip).  Quantised tensors travel as uint8 (OCP e4m3fn bytes) + fp32 scales.
 // mode 0: quant(x); 1: quant(rmsnorm(x) * w); 2: resid <- bf16(x + resid), quant(rmsnorm(resid) * w);
 // 3: x = [gate | up] rows of 2F, quant(silu(gate) * up)
@@ -1067,6 +1155,10 @@ TORCH_LIBRARY(chronos, m) {
     m.def("gemm_pp(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, bool prio) -> (Tensor, Tensor)");
     m.def("gemm_skinny(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, Tensor? we=None) "
           "-> (Tensor, Tensor)");
+    m.def("gemm_w4m(Tensor x, Tensor q, Tensor e, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps) "
+          "-> (Tensor, Tensor)");
+    m.def("gemm_w4m_configs() -> Tensor", &gemm_w4m_configs);
+    m.def("split_ticket_state(Tensor like) -> Tensor");
     m.def("gemv_resid(Tensor x, Tensor w, Tensor resid_in, Tensor(a!) resid_out, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("gemv_normp(Tensor s, Tensor part, float eps, Tensor w, bool swiglu, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("qkv_rope(Tensor x, Tensor? part, float eps, Tensor w, Tensor pos, Tensor tok_seq, "
@@ -1119,6 +1211,8 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("gemm", &gemm);
     m.impl("gemm_pp", &gemm_pp);
     m.impl("gemm_skinny", &gemm_skinny);
+    m.impl("gemm_w4m", &gemm_w4m);
+    m.impl("split_ticket_state", &split_ticket_state);
     m.impl("w4_expand", &w4_expand);
     m.impl("gemv_resid", &gemv_resid);
     m.impl("gemv_normp", &gemv_normp);

@@ -16,7 +16,10 @@ Routing is by measured shape:
   ``gemm_plan.json`` "w4plans" records it faster than the bf16 route by more than 3 % (``scripts/bench_skinny_w4.py``),
   the bf16 route on the dequantised copy everywhere else.  A packed-only Q4Tensor (no copy) takes the skinny kernel
   on every M <= 64 shape it accepts, and everywhere else the bf16 route on a scratch that one ``w4_expand`` launch
-  (csrc/kernels/w4_expand.hip) fills in front of the GEMM (``w4_dense``): the same bits as the copy;
+  (csrc/kernels/w4_expand.hip) fills in front of the GEMM (``w4_dense``): the same bits as the copy.  At M = 65-512
+  the fused W4A16 MFMA GEMM (csrc/kernels/gemm_w4m.hip) takes the call where ``gemm_plan.json`` "w4mplans" records a
+  win (``scripts/bench_mid_w4.py``): over the bf16 kernel on the copy (both modes) or only over expansion + that
+  kernel (packed-only tensors); a shape without a row runs the copy / the expansion as before;
 * hipBLASLt (torch.matmul) only where the plan records that the library wins by more than 3 % (the "plain library
   GEMM" rule), or for shapes the kernel does not take (K % 64, N % 4).  CHRONOS_PP=lib|own|auto forces a side.
 """
@@ -70,7 +73,8 @@ _SK = {0: (1, 1, 16), 1: (2, 1, 8), 2: (4, 1, 4), 3: (2, 2, 8), 4: (4, 2, 4), 5:
        7: (2, 8, 4), 8: (1, 2, 16), 9: (1, 4, 16), 10: (2, 4, 8), 11: (1, 1, 8)}
 SKINNY_MAX_M = 128
 # W4A16 mode of the same kernel (gemm_skinny.hip SK4_CONFIGS: mxfp4 q / e streamed, bf16 MFMA): own config ids ->
-# (RT, MT, NW); the unit is 128 k, so K % (128 NW split-K) == 0.  M <= 64 (MT <= 4).
+# (RT, MT, NW); the unit is 128 k, so K % (128 NW split-K) == 0.  M <= 64 (MT <= 4); above that, up to 512 rows, the
+# mid-M kernel of its own file takes over (gemm_w4m.hip, ``_W4M`` / ``W4_MID`` below).
 _SK4 = {0: (4, 1, 4), 1: (4, 1, 4), 2: (4, 1, 8), 3: (2, 1, 8), 4: (2, 1, 8), 5: (2, 1, 16), 6: (1, 1, 16),
         7: (4, 2, 4), 8: (2, 2, 8), 9: (4, 2, 8), 10: (4, 4, 4), 11: (2, 4, 8), 12: (2, 4, 4)}
 W4_SKINNY_MAX_M = 64
@@ -80,14 +84,30 @@ W4_SKINNY_MAX_M = 64
 # CHRONOS_PP=own).  Assigning it at run time is allowed: ``w4_plan`` drops the plan cache when it sees a new value.
 W4_SKINNY = os.environ.get("CHRONOS_W4_SKINNY", "plan")
 _w4_skinny_seen = W4_SKINNY
+# Above 64 rows, up to W4M_MAX_M, a Q4Tensor call can take the mid-M W4A16 GEMM (gemm_w4m.hip W4M_CONFIGS: config id ->
+# (WN: W rows per tile, XM: x rows per tile, ST: x ring stages); K % (128 split-K) == 0, N % WN == 0, SwiGLU
+# F % (WN / 2) == 0, any M).  Env CHRONOS_W4_MID (``W4_MID``, re-read like W4_SKINNY; a switch of its own, so that
+# W4_SKINNY = "model" keeps meaning what it meant): ``plan`` = the measured rows of gemm_plan.json "w4mplans", rows
+# [measured M, cfg, split-K, beats] read like "w4plans" — beats 2: faster than the routed bf16 kernel on the resident
+# copy, routed in both weight modes; beats 1: faster only than expansion + that kernel, routed for a packed-only tensor
+# alone; cfg < 0: measured, lost to both; no row: never measured, the copy / the expansion exactly as before (unlike
+# ``w4_plan(packed=True)`` the model pick is NOT substituted: an unmeasured mid-M kernel is not known to beat an
+# expansion) — ``off`` = the copy / the expansion everywhere, ``model`` = the ``_w4m_model`` pick for every valid shape
+# (the tests' way onto unmeasured shapes).  With beats = 1 rows the two weight modes run different kernels at those
+# points (same tolerance against the reference), as they already do at M <= 64.
+_W4M = {0: (64, 64, 4), 1: (128, 64, 4), 2: (64, 128, 4), 3: (128, 128, 4)}
+W4M_MIN_M, W4M_MAX_M = W4_SKINNY_MAX_M + 1, 512
+W4_MID = os.environ.get("CHRONOS_W4_MID", "plan")
+_w4_mid_seen = W4_MID
 _plan_cache: dict = {}
 _plan_table: Optional[dict] = None
 _qplan_table: Optional[dict] = None
 _w4plan_table: Optional[dict] = None
+_w4mplan_table: Optional[dict] = None
 
 
 def _plan_file() -> dict:
-    global _plan_table, _qplan_table, _w4plan_table
+    global _plan_table, _qplan_table, _w4plan_table, _w4mplan_table
     if _plan_table is None:
         import json
 
@@ -104,6 +124,7 @@ def _plan_file() -> dict:
         _plan_table = {key(k): rows for k, rows in raw.get("plans", {}).items()}
         _qplan_table = {key(k): rows for k, rows in raw.get("qplans", {}).items()}
         _w4plan_table = {key(k): rows for k, rows in raw.get("w4plans", {}).items()}
+        _w4mplan_table = {key(k): rows for k, rows in raw.get("w4mplans", {}).items()}
     return _plan_table
 
 
@@ -214,6 +235,63 @@ def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) 
         if packed and (out is None or not _sk4_valid(out[0], m, n, k, mode, out[1])):
             out = _sk4_model(m, n, k, mode)
     if out is not None and not _sk4_valid(out[0], m, n, k, mode, out[1]):
+        out = None
+    _plan_cache[key] = out
+    return out
+
+
+def _w4m_valid(c: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
+    """The binding's rules for the mid-M W4A16 GEMM (bindings.cpp gemm_w4m)."""
+    if c not in _W4M or sk < 1 or m < 1 or k < 1 or k > (1 << 20) or m * k >= (1 << 30) or n < 1:
+        return False
+    wn = _W4M[c][0]
+    if k % (128 * sk):
+        return False
+    return (n % 2 == 0 and (n // 2) % (wn // 2) == 0) if mode == PP_SWIGLU else n % wn == 0
+
+
+def _w4m_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tuple[int, int]]:
+    """Cost-model pick of a mid-M W4A16 config for a shape without a measured row: the x tile with the fewest padded
+    rows (then the wider one), split-K while the grid leaves CUs idle and a slice keeps at least a ring of stages, and
+    the wide W tile (half the x re-reads) only where its grid still covers the CUs."""
+    best = None
+    for c, (wn, xm, st) in _W4M.items():
+        tm = -(-m // xm)
+        tiles = tm * ((n // 2) // (wn // 2) if mode == PP_SWIGLU else n // wn)
+        for sk in (1, 2, 4, 7, 8):
+            if not _w4m_valid(c, m, n, k, mode, sk) or (sk > 1 and k // (128 * sk) < st):
+                continue
+            grid = tiles * sk
+            t = (tm * xm - m, -xm, sk > 1 and tiles >= cus, -min(grid, cus), sk, -wn, c)
+            if best is None or t < best[0]:
+                best = (t, (c, sk))
+    return best[1] if best else None
+
+
+def w4m_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) -> Optional[tuple[int, int]]:
+    """(config, split-K) of the mid-M W4A16 GEMM (gemm_w4m.hip) for a Q4Tensor projection at this shape, or None for
+    the bf16 route (the copy, or the expansion when ``packed``).  See ``W4_MID`` above for the plan's semantics."""
+    global _w4_mid_seen
+    if W4_MID != _w4_mid_seen:
+        _plan_cache.clear()
+        _w4_mid_seen = W4_MID
+    if not _W4A16_DECODE or W4_MID == "off" or m < W4M_MIN_M or m > W4M_MAX_M:
+        return None
+    key = ("w4mp" if packed else "w4m", m, n, k, mode)
+    hit = _plan_cache.get(key, False)
+    if hit is not False:
+        return hit
+    out = None
+    if W4_MID == "model":
+        out = _w4m_model(m, n, k, mode)
+    else:
+        _plan_file()
+        rows = (_w4mplan_table or {}).get((n, k, mode))
+        if rows:
+            pick = next((r for r in rows if m <= r[0]), None)  # no row at or above M: not measured
+            if pick is not None and pick[1] >= 0 and (pick[3] >= 2 or (pick[3] == 1 and packed)):
+                out = (int(pick[1]), int(pick[2]))
+    if out is not None and not _w4m_valid(out[0], m, n, k, mode, out[1]):
         out = None
     _plan_cache[key] = out
     return out
@@ -353,7 +431,8 @@ def gemv_q_ok(m: int, n: int, k: int) -> bool:
 # (a packed-only Q4Tensor has no ``.w``: there ``w4_dense`` expands it into the model's scratch, so the switch means
 # "expand everywhere" and gives copy mode's bits).
 # Above the GEMV's M, up to 64 rows, a Q4Tensor call takes the W4A16 mode of the skinny MFMA GEMM where ``w4_plan``
-# has a measured row for its shape (W4_SKINNY above).
+# has a measured row for its shape (W4_SKINNY above), and at 65-512 rows the mid-M W4A16 GEMM where ``w4m_plan`` has
+# one (W4_MID above).  The flag forces the copy / the expansion there too.
 _W4A16_DECODE = os.environ.get("CHRONOS_W4A16_DECODE", "1") != "0"
 # Largest M routed to the fp4 kernel (env CHRONOS_W4_MAX_M; the kernel takes up to 4).  Only what wins is routed:
 # on cold 8B weights the fp4 GEMV beats the bf16 GEMV on ``.w`` 1.30-1.75x at M = 1 on all four projections, and at
@@ -363,7 +442,7 @@ _W4A16_DECODE = os.environ.get("CHRONOS_W4A16_DECODE", "1") != "0"
 # W4A16 mode of the skinny MFMA GEMM instead (``w4_plan``), which does beat the routed bf16 kernel there.
 W4_MAX_M = int(os.environ.get("CHRONOS_W4_MAX_M", "1"))
 # fp4 GEMV / W4A16 skinny GEMM launches issued from Python (captured graphs replay them uncounted)
-w4_stats = {"gemv_launches": 0, "skinny_launches": 0, "expand_launches": 0}
+w4_stats = {"gemv_launches": 0, "skinny_launches": 0, "expand_launches": 0, "mid_launches": 0}
 
 
 def is_w4(w) -> bool:
@@ -469,6 +548,29 @@ def _w4_skinny(x, w, mode: int, m: int, resid=None):
     return _k().gemm_skinny(x.reshape(-1, k), w.q, mode, plan[0], plan[1], resid, None, 1e-5, w.e)
 
 
+def _w4_mid(x, w, mode: int, m: int, resid=None):
+    """The mid-M W4A16 launch (gemm_w4m.hip) for a Q4Tensor call neither the GEMV nor the skinny kernel took: (y,
+    partials), or None when ``w4m_plan`` has no route (the caller substitutes ``w4_dense``).  A fusable LazyNorm goes in
+    as the kernel's NORMP prologue."""
+    if m < W4M_MIN_M or m > W4M_MAX_M:
+        return None
+    lazy = isinstance(x, LazyNorm)
+    t = x.s if lazy else x
+    if not t.is_cuda:
+        return None
+    k = t.shape[-1]
+    plan = w4m_plan(m, w.shape[0], k, mode, w.w is None)
+    if plan is None:
+        return None
+    from . import _k
+
+    w4_stats["mid_launches"] += 1
+    if lazy and x.fusable() and mode != PP_RESID:
+        return _k().gemm_w4m(x.s.reshape(-1, k), w.q, w.e, mode, plan[0], plan[1], None, x.part, x.eps)
+    x = LazyNorm.force(x)
+    return _k().gemm_w4m(x.reshape(-1, k), w.q, w.e, mode, plan[0], plan[1], resid, None, 1e-5)
+
+
 def _q_fallback(x, w, swiglu: bool = False) -> torch.Tensor:
     """fp8 weight off the W8A16 GEMV shapes: quantise the activations and run the W8A8 op."""
     from . import qlinear, quant_rows
@@ -493,6 +595,8 @@ def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOu
             part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, None, w.e)
             return ResidOut(s, part)
         hit = _w4_skinny(x, w, PP_RESID, m, resid.reshape(m, -1))
+        if hit is None:
+            hit = _w4_mid(x, w, PP_RESID, m, resid.reshape(m, -1))
         if hit is not None:
             return ResidOut(hit[0].view(resid.shape), hit[1])
         w = w4_dense(w)
@@ -565,6 +669,8 @@ def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
             y = _k().gemv(x.reshape(-1, k), w_gu.q, True, None, w_gu.e)
             return y.view(*x.shape[:-1], y.shape[-1])
         hit = _w4_skinny(x, w_gu, PP_SWIGLU, m)
+        if hit is None:
+            hit = _w4_mid(x, w_gu, PP_SWIGLU, m)
         if hit is not None:
             return hit[0].view(*x.shape[:-1], n // 2)
         w_gu = w4_dense(w_gu)
@@ -613,6 +719,8 @@ def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
             y = _k().gemv(x.reshape(-1, k), w.q, False, None, w.e)
             return y.view(*x.shape[:-1], n)
         hit = _w4_skinny(x, w, PP_PLAIN, m) if out is None else None
+        if hit is None and out is None:
+            hit = _w4_mid(x, w, PP_PLAIN, m)
         if hit is not None:
             return hit[0].view(*x.shape[:-1], n)
         w = w4_dense(w)
