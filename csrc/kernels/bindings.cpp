@@ -738,15 +738,85 @@ static int32_t* split_tickets(const Tensor& x, int64_t n) {
     return it->second.data_ptr<int32_t>();
 }
 
-// Batched projection GEMM family (gemm_pp.hip): y = x @ w.T with a fused epilogue, M >= 3.
-//   mode 0 plain (y [M, N]); 1 swiglu (w = [gate; up] [2F, K], y [M, F] = silu(x Wg^T) * (x Wu^T)); 2 resid (y = the
-//   new residual stream bf16(bf16(x @ w.T) + resid), second output = per-row partial sums of y^2 [M, N / (BN/4)]).
-//   part_in given (modes 0/1): x is the raw residual stream s and the folded input RMSNorm is applied as the per-row
-//   scale rsqrt(sum(part_in[m]) / K + eps).  cfg = tile config (gemm_pp_bm / gemm_pp_bn), splitk divides K / 64.
+// ---- what the three projection GEMM ops (gemm_pp, gemm_skinny, gemm_w4m) share -----------------------------------
+// x bf16 [M, K] (any leading dims), one fused epilogue by mode: 0 plain (y [M, N]); 1 swiglu (w = [gate; up] [2F, K],
+// y [M, F] = silu(x Wg^T) * (x Wu^T)); 2 resid (y = the new residual stream bf16(bf16(x @ w.T) + resid), second output =
+// per-row partial sums of y^2, one per ``pcols`` output columns of the family).  part_in given (modes 0 / 1): x is the
+// raw residual stream s and the folded input RMSNorm is applied as the per-row scale rsqrt(sum(part_in[m]) / K + eps).
+struct GemmIO {
+    Tensor y, part_out, ws;  // ws: the split-K workspace, alive until the launch is enqueued
+};
+
+inline void chk_gemm_x(const std::string& op, const Tensor& x, int64_t mode, const c10::optional<Tensor>& part_in) {
+    chk_bf16(x, "x");
+    CHK(x.dim() >= 1 && x.size(-1) > 0, op + ": x must be [M, K]");
+    CHK(mode >= 0 && mode <= 2, op + ": mode");
+    CHK(mode != 2 || !part_in.has_value(), op + ": resid mode has no norm prologue");
+}
+
+// mxfp4 weights (OCP MXFP4): q = packed e2m1 bytes [N, K / 2], e = e8m0 block scales [N, K / 32], on x's device
+inline void chk_mxfp4(const std::string& op, const Tensor& x, const Tensor& q, const char* qn, const Tensor& e,
+                      const char* en) {
+    chk_gpu(q, qn);
+    chk_gpu(e, en);
+    const int64_t K = x.size(-1), N = q.size(0);
+    CHK(q.scalar_type() == at::kByte && q.dim() == 2 && K % 32 == 0 && q.size(1) == K / 2,
+        op + ": " + qn + " must be uint8 [N, K / 2]");
+    CHK(e.scalar_type() == at::kByte && e.dim() == 2 && e.size(0) == N && e.size(1) == K / 32,
+        op + ": " + en + " must be uint8 [N, K / 32]");
+    CHK(q.device() == x.device() && e.device() == x.device(), op + ": " + qn + " / " + en + " on x's device");
+}
+
+// Fills the operand-independent part of the launch arguments: sizes, the output by mode, resid with the kResid
+// partials [M, N / pcols], the norm prologue's partials.  Call with x's device current, after the shape checks.
+static GemmIO gemm_io(const std::string& op, chronos::PPArgs& a, const Tensor& x, int64_t N, int64_t mode,
+                      int64_t splitk, double eps, const c10::optional<Tensor>& resid,
+                      const c10::optional<Tensor>& part_in, int64_t pcols) {
+    const int64_t K = x.size(-1), M = x.numel() / K;
+    GemmIO io;
+    a.x = bf(x);
+    a.M = (int)M;
+    a.N = (int)N;
+    a.K = (int)K;
+    a.F = (int)(N / 2);
+    a.splitk = (int)splitk;
+    a.eps = (float)eps;
+    io.y = at::empty({M, mode == 1 ? N / 2 : N}, x.options());
+    a.y = bfm(io.y);
+    if (mode == 2) {
+        CHK(resid.has_value(), op + ": resid mode needs resid");
+        chk_bf16(*resid, "resid");
+        CHK(resid->numel() == M * N && resid->device() == x.device(), op + ": resid must be [M, N] on x's device");
+        a.resid = bf(*resid);
+        io.part_out = at::empty({M, N / pcols}, x.options().dtype(at::kFloat));
+        a.part_out = io.part_out.data_ptr<float>();
+    }
+    if (part_in.has_value()) {
+        chk_gpu(*part_in, "part_in");
+        CHK(part_in->scalar_type() == at::kFloat && part_in->dim() == 2 && part_in->size(0) == M &&
+                part_in->size(1) >= 1 && part_in->device() == x.device(),
+            op + ": part_in must be f32 [M, P] on x's device");
+        a.part_in = part_in->data_ptr<float>();
+        a.nparts_in = (int)part_in->size(1);
+    }
+    return io;
+}
+
+// Split-K: ``floats`` f32 of workspace per (workgroup group, slice) and one ticket per group
+static void gemm_splitk(chronos::PPArgs& a, GemmIO& io, const Tensor& x, int64_t groups, int64_t floats) {
+    if (a.splitk > 1) {
+        io.ws = at::empty({groups * a.splitk * floats}, x.options().dtype(at::kFloat));
+        a.ws = io.ws.data_ptr<float>();
+        a.cnt = split_tickets(x, groups);
+    }
+}
+
+// Batched projection GEMM family (gemm_pp.hip, gemm_lg.hip), M >= 3: w bf16 [N, K]; the kResid partials are
+// [M, N / (BN / 4)] (gemm_lg: BN / 2).  cfg = tile config (gemm_pp_bm / gemm_pp_bn), splitk divides K / 64.
 std::tuple<Tensor, Tensor> gemm_pp(const Tensor& x, const Tensor& w, int64_t mode, int64_t cfg, int64_t splitk,
                                    const c10::optional<Tensor>& resid, const c10::optional<Tensor>& part_in,
                                    double eps, bool prio) {
-    chk_bf16(x, "x");
+    chk_gemm_x("gemm_pp", x, mode, part_in);
     chk_bf16(w, "w");
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
     CHK(w.dim() == 2 && w.size(1) == K, "gemm_pp: w must be [N, K]");
@@ -755,10 +825,8 @@ std::tuple<Tensor, Tensor> gemm_pp(const Tensor& x, const Tensor& w, int64_t mod
     CHK((cfg >= 0 && cfg < chronos::kPPConfigs + chronos::kLGConfigs) ||
             (chronos::gemm_lg_ablations_built() && cfg >= 40 && cfg < 72) ||
             (cfg >= chronos::kLGTinyFirst && cfg < chronos::kLGTinyFirst + chronos::kLGTinyConfigs), "gemm_pp: cfg");
-    CHK(mode >= 0 && mode <= 2, "gemm_pp: mode");
     const int BM = lg ? chronos::gemm_lg_xm((int)cfg) : chronos::gemm_pp_bm((int)cfg);
     const int BN = lg ? chronos::gemm_lg_wn((int)cfg) : chronos::gemm_pp_bn((int)cfg);
-    const int PCOLS = lg ? BN / 2 : BN / 4;  // output columns per RMSNorm partial (kResid)
     // gemm_lg addresses both operands through buffer descriptors: 32-bit byte offsets, with one tile of slack
     CHK(!lg || ((N + BN) * K * 2 < (1LL << 31) && (M + BM) * K * 2 < (1LL << 31)), "gemm_lg: operand > 2 GiB");
     CHK(M >= 1 && M < (1LL << 31) / BM && K % 64 == 0 && K <= (1 << 20) && N * K < (1LL << 40), "gemm_pp: size");
@@ -766,207 +834,93 @@ std::tuple<Tensor, Tensor> gemm_pp(const Tensor& x, const Tensor& w, int64_t mod
     CHK(!lg || splitk == 1 || chronos::gemm_lg_splitk_ok((int)cfg), "gemm_lg: this config has no split-K");
     CHK(mode == 0 ? N % 4 == 0 : N % BN == 0, "gemm_pp: N % 4 (plain) / N % BN (swiglu, resid)");
     CHK(mode != 1 || (lg ? (BN / 4) % 16 == 0 : (BN / 8) % 16 == 0), "gemm_pp: swiglu needs BN >= 128 (gemm_lg: 64)");
-    CHK(mode != 2 || !part_in.has_value(), "gemm_pp: resid mode has no norm prologue");
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     chronos::PPArgs a{};
-    a.x = bf(x);
+    GemmIO io = gemm_io("gemm_pp", a, x, N, mode, splitk, eps, resid, part_in, lg ? BN / 2 : BN / 4);
     a.w = bf(w);
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.F = (int)(N / 2);
-    a.splitk = (int)splitk;
     a.kts = (int)(K / 64 / splitk);
-    a.eps = (float)eps;
     // timing-only diagnostics (wrong results by design): honoured only in a CHRONOS_GEMM_ABLATIONS build
     a.ablate = chronos::gemm_lg_ablations_built() ? chronos::knob("pp_ablate", 0) : 0;
     a.gm = chronos::knob("pp_gm", 8);  // +7-9 % at M = 16384 (profiles/r3_gemm_tile_order_m16384.jsonl)
     a.handoff = chronos::knob("lg_handoff", -1);
-    Tensor y = at::empty({M, mode == 1 ? N / 2 : N}, x.options());
-    a.y = bfm(y);
-    Tensor part_out;
-    if (mode == 2) {
-        CHK(resid.has_value(), "gemm_pp: resid mode needs resid");
-        chk_bf16(*resid, "resid");
-        CHK(resid->numel() == M * N, "gemm_pp: resid must be [M, N]");
-        a.resid = bf(*resid);
-        part_out = at::empty({M, N / PCOLS}, x.options().dtype(at::kFloat));
-        a.part_out = part_out.data_ptr<float>();
-    }
-    if (part_in.has_value()) {
-        chk_gpu(*part_in, "part_in");
-        CHK(part_in->scalar_type() == at::kFloat && part_in->dim() == 2 && part_in->size(0) == M, "part_in [M, P] f32");
-        a.part_in = part_in->data_ptr<float>();
-        a.nparts_in = (int)part_in->size(1);
-    }
     const int64_t tiles = ((M + BM - 1) / BM) * (mode == 1 ? (N / 2) / (BN / 2) : (N + BN - 1) / BN);
-    Tensor ws;
-    if (splitk > 1) {
-        ws = at::empty({tiles * splitk * BM * BN}, x.options().dtype(at::kFloat));
-        a.ws = ws.data_ptr<float>();
-        a.cnt = split_tickets(x, tiles);
-    }
+    gemm_splitk(a, io, x, tiles, (int64_t)BM * BN);
     if (lg) {
         CHK(!prio && chronos::launch_gemm_lg((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()), "gemm_lg: launch");
     } else {
         CHK(chronos::launch_gemm_pp((int)cfg, (int)mode, part_in.has_value(), prio, a, cur_stream()), "gemm_pp: launch");
     }
-    return {y, part_out};
+    return {io.y, io.part_out};
 }
 
-// Skinny-M GEMM (gemm_skinny.hip), M <= 16 * MT of the config: same epilogues and tensors as gemm_pp; the kResid
-// partials are [M, N / (16 * RT)].  With ``we`` the W4A16 weight mode: w = packed e2m1 bytes [N, K / 2], we = e8m0 block
-// scales [N, K / 32] (OCP MXFP4), cfg an id of the W4 config table, K % (128 * NW * splitk) == 0.
+// Skinny-M GEMM (gemm_skinny.hip), M <= 16 * MT of the config: the kResid partials are [M, N / (16 * RT)].  With ``we``
+// the W4A16 weight mode: w / we = mxfp4 q / e, cfg an id of the W4 config table, K % (128 * NW * splitk) == 0.
 std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t mode, int64_t cfg, int64_t splitk,
                                        const c10::optional<Tensor>& resid, const c10::optional<Tensor>& part_in,
                                        double eps, const c10::optional<Tensor>& we) {
-    chk_bf16(x, "x");
+    chk_gemm_x("gemm_skinny", x, mode, part_in);
     const bool w4 = we.has_value();
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
     if (w4) {
-        chk_gpu(w, "w");
-        chk_gpu(*we, "we");
-        CHK(w.scalar_type() == at::kByte && w.dim() == 2 && K % 32 == 0 && w.size(1) == K / 2,
-            "gemm_skinny: mxfp4 w must be uint8 [N, K / 2]");
-        CHK(we->scalar_type() == at::kByte && we->dim() == 2 && we->size(0) == N && we->size(1) == K / 32,
-            "gemm_skinny: we must be uint8 [N, K / 32]");
-        CHK(w.is_contiguous() && we->is_contiguous() && w.device() == x.device() && we->device() == x.device(),
-            "gemm_skinny: w / we contiguous, on x's device");
+        chk_mxfp4("gemm_skinny", x, w, "w", *we, "we");
         CHK(cfg >= 0 && cfg < chronos::kSkinnyW4Configs, "gemm_skinny: W4 cfg");
     } else {
         chk_bf16(w, "w");
         CHK(w.dim() == 2 && w.size(1) == K, "gemm_skinny: w must be [N, K]");
         CHK(cfg >= 0 && cfg < chronos::kSkinnyConfigs, "gemm_skinny: cfg");
     }
-    CHK(mode >= 0 && mode <= 2, "gemm_skinny: mode");
     const int RT = w4 ? chronos::gemm_skinny_w4_rt((int)cfg) : chronos::gemm_skinny_rt((int)cfg);
     const int MT = w4 ? chronos::gemm_skinny_w4_mt((int)cfg) : chronos::gemm_skinny_mt((int)cfg);
     const int NW = w4 ? chronos::gemm_skinny_w4_nw((int)cfg) : chronos::gemm_skinny_nw((int)cfg);
     CHK(M >= 1 && M <= 16 * MT, "gemm_skinny: M must be in [1, 16 * MT] of the config");
-    if (w4) {
-        CHK(splitk >= 1 && K % (128 * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
-            "gemm_skinny: W4 K % (128 * NW * splitk) == 0");
-    } else {
-        CHK(splitk >= 1 && K % (64 * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
-            "gemm_skinny: K % (64 * NW * splitk) == 0");
-    }
+    CHK(splitk >= 1 && K % ((w4 ? 128 : 64) * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
+        w4 ? "gemm_skinny: W4 K % (128 * NW * splitk) == 0" : "gemm_skinny: K % (64 * NW * splitk) == 0");
     CHK(mode == 1 ? RT % 2 == 0 && (N / 2) % (8 * RT) == 0 && N % 2 == 0 : N % (16 * RT) == 0,
         "gemm_skinny: N % (16 RT) (swiglu: F % (8 RT), RT even)");
-    CHK(mode != 2 || !part_in.has_value(), "gemm_skinny: resid mode has no norm prologue");
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     chronos::PPArgs a{};
-    a.x = bf(x);
+    GemmIO io = gemm_io("gemm_skinny", a, x, N, mode, splitk, eps, resid, part_in, 16 * RT);
     if (w4) {
         a.w = reinterpret_cast<const uint16_t*>(w.data_ptr<uint8_t>());
         a.wexp = we->data_ptr<uint8_t>();
     } else {
         a.w = bf(w);
     }
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.F = (int)(N / 2);
-    a.splitk = (int)splitk;
-    a.eps = (float)eps;
-    Tensor y = at::empty({M, mode == 1 ? N / 2 : N}, x.options());
-    a.y = bfm(y);
-    Tensor part_out;
-    if (mode == 2) {
-        CHK(resid.has_value(), "gemm_skinny: resid mode needs resid");
-        chk_bf16(*resid, "resid");
-        CHK(resid->numel() == M * N, "gemm_skinny: resid must be [M, N]");
-        a.resid = bf(*resid);
-        part_out = at::empty({M, N / (16 * RT)}, x.options().dtype(at::kFloat));
-        a.part_out = part_out.data_ptr<float>();
-    }
-    if (part_in.has_value()) {
-        chk_gpu(*part_in, "part_in");
-        CHK(part_in->scalar_type() == at::kFloat && part_in->dim() == 2 && part_in->size(0) == M, "part_in [M, P] f32");
-        a.part_in = part_in->data_ptr<float>();
-        a.nparts_in = (int)part_in->size(1);
-    }
-    const int64_t groups = mode == 1 ? (N / 2) / (8 * RT) : N / (16 * RT);
-    Tensor ws;
-    if (splitk > 1) {
-        ws = at::empty({groups * splitk * 64 * RT * MT * 4}, x.options().dtype(at::kFloat));
-        a.ws = ws.data_ptr<float>();
-        a.cnt = split_tickets(x, groups);
-    }
+    gemm_splitk(a, io, x, mode == 1 ? (N / 2) / (8 * RT) : N / (16 * RT), (int64_t)64 * RT * MT * 4);
     if (w4) {
         CHK(chronos::launch_gemm_skinny_w4((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()),
             "gemm_skinny: W4 launch");
     } else {
         CHK(chronos::launch_gemm_skinny((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()), "gemm_skinny: launch");
     }
-    return {y, part_out};
+    return {io.y, io.part_out};
 }
 
-// Mid-M W4A16 GEMM (gemm_w4m.hip): x bf16 [M, K], q uint8 [N, K / 2] packed e2m1, e uint8 [N, K / 32] e8m0 (OCP
-// MXFP4); same modes, resid / part_in / eps and outputs as gemm_skinny.  cfg indexes W4M_CONFIGS (tile = WN W rows x XM
-// x rows, any M >= 1), K % (128 * splitk) == 0, N % WN == 0 (swiglu: F % (WN / 2) == 0); the kResid partials are
-// [M, N / (WN / 2)].
+// Mid-M W4A16 GEMM (gemm_w4m.hip): q / e = mxfp4 weights.  cfg indexes W4M_CONFIGS (tile = WN W rows x XM x rows, any
+// M >= 1), K % (128 * splitk) == 0, N % WN == 0 (swiglu: F % (WN / 2) == 0); the kResid partials are [M, N / (WN / 2)].
 std::tuple<Tensor, Tensor> gemm_w4m(const Tensor& x, const Tensor& q, const Tensor& e, int64_t mode, int64_t cfg,
                                     int64_t splitk, const c10::optional<Tensor>& resid,
                                     const c10::optional<Tensor>& part_in, double eps) {
-    chk_bf16(x, "x");
-    chk_gpu(q, "q");
-    chk_gpu(e, "e");
-    CHK(x.dim() >= 1 && x.size(-1) > 0, "gemm_w4m: x must be [M, K]");
+    chk_gemm_x("gemm_w4m", x, mode, part_in);
+    chk_mxfp4("gemm_w4m", x, q, "q", e, "e");
     const int64_t K = x.size(-1), M = x.numel() / K, N = q.size(0);
-    CHK(q.scalar_type() == at::kByte && q.dim() == 2 && K % 32 == 0 && q.size(1) == K / 2,
-        "gemm_w4m: q must be uint8 [N, K / 2]");
-    CHK(e.scalar_type() == at::kByte && e.dim() == 2 && e.size(0) == N && e.size(1) == K / 32,
-        "gemm_w4m: e must be uint8 [N, K / 32]");
-    CHK(q.device() == x.device() && e.device() == x.device(), "gemm_w4m: q / e on x's device");
     CHK(cfg >= 0 && cfg < chronos::kW4MConfigs, "gemm_w4m: cfg");
-    CHK(mode >= 0 && mode <= 2, "gemm_w4m: mode");
     const int WN = chronos::gemm_w4m_wn((int)cfg), XM = chronos::gemm_w4m_xm((int)cfg);
     // x is addressed through a buffer descriptor: 32-bit byte offsets
     CHK(M >= 1 && K <= (1 << 20) && M * K < (1LL << 30) && N * K < (1LL << 40), "gemm_w4m: size (M K < 2^30)");
     CHK(splitk >= 1 && K % (128 * splitk) == 0, "gemm_w4m: K % (128 * splitk) == 0");
     CHK(mode == 1 ? N % 2 == 0 && (N / 2) % (WN / 2) == 0 : N % WN == 0,
         "gemm_w4m: N % WN (swiglu: F % (WN / 2)) == 0");
-    CHK(mode != 2 || !part_in.has_value(), "gemm_w4m: resid mode has no norm prologue");
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     chronos::PPArgs a{};
-    a.x = bf(x);
+    GemmIO io = gemm_io("gemm_w4m", a, x, N, mode, splitk, eps, resid, part_in, WN / 2);
     a.w = reinterpret_cast<const uint16_t*>(q.data_ptr<uint8_t>());
     a.wexp = e.data_ptr<uint8_t>();
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.F = (int)(N / 2);
-    a.splitk = (int)splitk;
-    a.eps = (float)eps;
-    Tensor y = at::empty({M, mode == 1 ? N / 2 : N}, x.options());
-    a.y = bfm(y);
-    Tensor part_out;
-    if (mode == 2) {
-        CHK(resid.has_value(), "gemm_w4m: resid mode needs resid");
-        chk_bf16(*resid, "resid");
-        CHK(resid->numel() == M * N && resid->device() == x.device(), "gemm_w4m: resid must be [M, N] on x's device");
-        a.resid = bf(*resid);
-        part_out = at::empty({M, N / (WN / 2)}, x.options().dtype(at::kFloat));
-        a.part_out = part_out.data_ptr<float>();
-    }
-    if (part_in.has_value()) {
-        chk_gpu(*part_in, "part_in");
-        CHK(part_in->scalar_type() == at::kFloat && part_in->dim() == 2 && part_in->size(0) == M &&
-                part_in->size(1) >= 1 && part_in->device() == x.device(),
-            "gemm_w4m: part_in must be f32 [M, P] on x's device");
-        a.part_in = part_in->data_ptr<float>();
-        a.nparts_in = (int)part_in->size(1);
-    }
     const int64_t tiles = ((M + XM - 1) / XM) * (mode == 1 ? (N / 2) / (WN / 2) : N / WN);
     CHK(tiles * splitk < (1LL << 31), "gemm_w4m: grid");
-    Tensor ws;
-    if (splitk > 1) {
-        ws = at::empty({tiles * splitk * WN * XM}, x.options().dtype(at::kFloat));
-        a.ws = ws.data_ptr<float>();
-        a.cnt = split_tickets(x, tiles);
-    }
+    gemm_splitk(a, io, x, tiles, (int64_t)WN * XM);
     CHK(chronos::launch_gemm_w4m((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()), "gemm_w4m: launch");
-    return {y, part_out};
+    return {io.y, io.part_out};
 }
 
 // [kW4MConfigs, 3] int64 on the CPU: (WN, XM, ST) per config id, so that ops/gemm.py's table can be pinned to the kernel's

@@ -14,6 +14,7 @@ import os
 
 import torch
 
+from . import gemm
 from . import reference as ref
 from .gemm import (LazyNorm, ResidOut, W4Scratch, gate_up_silu, gemv_ok, gemv_q_ok, gemv_resid,  # noqa: F401
                    gemv_w4_ok, is_q, is_w4, linear, resid_ok, w4_dense, w4_expand)
@@ -188,22 +189,14 @@ def qkv_rope(x, w_qkv, pos, tok_seq, block_table, cos_sin, q_out, k_cache, v_cac
         return False
     t = x.s if lazy else x
     m, n, k = t.numel() // t.shape[-1], w_qkv.shape[0], t.shape[-1]
-    if is_w4(w_qkv):  # mxfp4 weights: the W4A16 GEMV at its shapes, else the bf16 copy through the code below
-        from .gemm import _w4_route
-
-        if _w4_route(t, m, n, k, 2):
-            _k().qkv_rope(t.reshape(m, k), x.part if lazy else None, x.eps if lazy else 0.0, w_qkv.q, pos, tok_seq,
-                          block_table, cos_sin, q_out, k_cache, v_cache, hq, hkv, k_scale, v_scale, None, w_qkv.e)
-            return True
-        if not (t.is_cuda and m <= 2 and gemv_ok(m, n, k)):  # (before w4_dense: no expansion for a call not made)
-            return False
-        w_qkv = w4_dense(w_qkv)
-    fp8w = is_q(w_qkv)  # fp8 weights: the W8A16 GEMV (e4m3 bytes + per-row scales)
-    if not (t.is_cuda and m <= 2 and (gemv_q_ok(m, n, k) if fp8w else gemv_ok(m, n, k))):
+    pick = gemm.decode_gemv_weight(t, w_qkv, m, n, k)  # bf16, fp8 bytes + row scales, or mxfp4 q + block scales
+    if pick is None:
         return False
-    _k().qkv_rope(t.reshape(m, k), x.part if lazy else None, x.eps if lazy else 0.0, w_qkv.q if fp8w else w_qkv,
-                  pos, tok_seq, block_table, cos_sin, q_out, k_cache, v_cache, hq, hkv, k_scale, v_scale,
-                  w_qkv.s if fp8w else None)
+    w, ws, we = pick
+    if we is not None:
+        gemm.w4_stats["gemv_launches"] += 1
+    _k().qkv_rope(t.reshape(m, k), x.part if lazy else None, x.eps if lazy else 0.0, w, pos, tok_seq, block_table,
+                  cos_sin, q_out, k_cache, v_cache, hq, hkv, k_scale, v_scale, ws, we)
     return True
 
 

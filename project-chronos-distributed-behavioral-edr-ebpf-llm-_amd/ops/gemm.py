@@ -1,33 +1,36 @@
 """Projection GEMMs.
 
-``linear(x, w)`` computes ``x @ w.T`` for weights stored [out, in] (HF layout); ``gate_up_silu`` is the fused K8+K9.
-Routing is by measured shape:
+``linear(x, w)`` computes ``x @ w.T`` for weights stored [out, in] (HF layout); ``gate_up_silu`` is the fused K8+K9 and
+``gemv_resid`` the O / down producer with the residual add + RMSNorm partial sums as its epilogue (-> ResidOut).  All
+three are one dispatcher, ``_project``, which walks one ladder by weight kind and then by measured shape:
 
-* M <= 2 (single-stream decode): the hand-written GEMV (csrc/kernels/gemv.hip), 1 KiB row-contiguous weight
-  streaming — beats hipBLASLt on every decode shape;
-* M >= 3: the hand-written MFMA GEMM families with their fused epilogues — the decoder's residual add + RMSNorm
-  partial sums on O / down (``gemv_resid`` -> ResidOut), the folded RMSNorm as a per-row scale on QKV / gate_up / LM
-  head (a LazyNorm input), SwiGLU on gate_up: the skinny-M weight-streaming kernel (csrc/kernels/gemm_skinny.hip,
-  M <= 128: jump-forward forwards, tail decode buckets) and the ping-pong tile GEMM (csrc/kernels/gemm_pp.hip) above,
-  with the kernel, tile config and split-K of the measured plan (``gemm_plan.json``: per (N, K, epilogue) the best
-  by M range, from ``scripts/tune_gemm_pp.py`` on one MI355X, random operands, cold weights; plan cfg >= 100 is
-  skinny config cfg - 100);
-* MXFP4 weights (a Q4Tensor): the W4A16 GEMV at M = 1, the W4A16 mode of the skinny kernel at M = 2-64 where
-  ``gemm_plan.json`` "w4plans" records it faster than the bf16 route by more than 3 % (``scripts/bench_skinny_w4.py``),
-  the bf16 route on the dequantised copy everywhere else.  A packed-only Q4Tensor (no copy) takes the skinny kernel
-  on every M <= 64 shape it accepts, and everywhere else the bf16 route on a scratch that one ``w4_expand`` launch
-  (csrc/kernels/w4_expand.hip) fills in front of the GEMM (``w4_dense``): the same bits as the copy.  At M = 65-512
-  the fused W4A16 MFMA GEMM (csrc/kernels/gemm_w4m.hip) takes the call where ``gemm_plan.json`` "w4mplans" records a
-  win (``scripts/bench_mid_w4.py``): over the bf16 kernel on the copy (both modes) or only over expansion + that
-  kernel (packed-only tensors); a shape without a row runs the copy / the expansion as before;
+* MXFP4 weights (a Q4Tensor): the W4A16 GEMV (csrc/kernels/gemv.hip W4) at M = 1 (``W4_MAX_M``); the W4A16 mode of the
+  skinny kernel (csrc/kernels/gemm_skinny.hip) at M = 2-64 where ``gemm_plan.json`` "w4plans" records it faster than
+  the bf16 route by more than 3 % (``scripts/bench_skinny_w4.py``); the fused W4A16 MFMA GEMM
+  (csrc/kernels/gemm_w4m.hip) at M = 65-512 where "w4mplans" records a win (``scripts/bench_mid_w4.py``): over the bf16
+  kernel on the copy (both modes) or only over expansion + that kernel (packed-only tensors).  Everything else runs
+  the bf16 steps below on ``w4_dense(w)``: the resident copy, or for a packed-only Q4Tensor (no copy) a scratch that
+  one ``w4_expand`` launch (csrc/kernels/w4_expand.hip) fills in front of the GEMM, the same bits as the copy.  A
+  packed-only tensor takes the skinny kernel on every M <= 64 shape it accepts (``w4_plan(packed=True)``);
+* fp8 weights (a QTensor): the W8A16 GEMV at its shapes (M <= 4; the fused norm and the residual producer: M <= 2),
+  else the activations are quantised and the W8A8 op runs (``ops.qlinear``, routed by "qplans");
+* bf16 weights, M <= ``GEMV_MAX_M`` (1: single-stream decode): the hand-written GEMV (csrc/kernels/gemv.hip), 1 KiB
+  row-contiguous weight streaming — beats hipBLASLt on every decode shape;
+* bf16 weights above: the hand-written MFMA GEMM families with their fused epilogues — the residual epilogue, the
+  folded RMSNorm of a LazyNorm input as a per-row scale, SwiGLU on gate_up: the skinny-M weight-streaming kernel
+  (M <= 128: jump-forward forwards, tail decode buckets) and the tile GEMMs (csrc/kernels/gemm_pp.hip, gemm_lg.hip)
+  above, with the kernel, tile config and split-K of the measured plan (``gemm_plan.json`` "plans": per (N, K,
+  epilogue) the best by M range, from ``scripts/tune_gemm_pp.py`` on one MI355X, random operands, cold weights; plan
+  cfg >= 100 is skinny config cfg - 100);
 * hipBLASLt (torch.matmul) only where the plan records that the library wins by more than 3 % (the "plain library
-  GEMM" rule), or for shapes the kernel does not take (K % 64, N % 4).  CHRONOS_PP=lib|own|auto forces a side.
+  GEMM" rule), for shapes the kernels do not take (K % 64, N % 4) and for ``linear(out=)``.  CHRONOS_PP=lib|own|auto
+  forces a side.
 """
 from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Callable, Optional
+from typing import Optional
 
 import torch
 
@@ -81,12 +84,11 @@ W4_SKINNY_MAX_M = 64
 # Which Q4Tensor calls above the fp4 GEMV's M take the W4A16 skinny kernel (env CHRONOS_W4_SKINNY): ``plan`` = the
 # measured rows of gemm_plan.json "w4plans" (a shape with no row runs the bf16 copy), ``off`` = the copy everywhere,
 # ``model`` = the ``_sk4_model`` pick for every valid shape (the tests' way to the kernel on unmeasured shapes, like
-# CHRONOS_PP=own).  Assigning it at run time is allowed: ``w4_plan`` drops the plan cache when it sees a new value.
+# CHRONOS_PP=own).  Like every switch here it may be assigned at run time: the plan cache is keyed by the switches.
 W4_SKINNY = os.environ.get("CHRONOS_W4_SKINNY", "plan")
-_w4_skinny_seen = W4_SKINNY
 # Above 64 rows, up to W4M_MAX_M, a Q4Tensor call can take the mid-M W4A16 GEMM (gemm_w4m.hip W4M_CONFIGS: config id ->
 # (WN: W rows per tile, XM: x rows per tile, ST: x ring stages); K % (128 split-K) == 0, N % WN == 0, SwiGLU
-# F % (WN / 2) == 0, any M).  Env CHRONOS_W4_MID (``W4_MID``, re-read like W4_SKINNY; a switch of its own, so that
+# F % (WN / 2) == 0, any M).  Env CHRONOS_W4_MID (``W4_MID``, assignable like W4_SKINNY; a switch of its own, so that
 # W4_SKINNY = "model" keeps meaning what it meant): ``plan`` = the measured rows of gemm_plan.json "w4mplans", rows
 # [measured M, cfg, split-K, beats] read like "w4plans" — beats 2: faster than the routed bf16 kernel on the resident
 # copy, routed in both weight modes; beats 1: faster only than expansion + that kernel, routed for a packed-only tensor
@@ -98,16 +100,16 @@ _w4_skinny_seen = W4_SKINNY
 _W4M = {0: (64, 64, 4), 1: (128, 64, 4), 2: (64, 128, 4), 3: (128, 128, 4)}
 W4M_MIN_M, W4M_MAX_M = W4_SKINNY_MAX_M + 1, 512
 W4_MID = os.environ.get("CHRONOS_W4_MID", "plan")
-_w4_mid_seen = W4_MID
-_plan_cache: dict = {}
+# The measured plans: gemm_plan.json (env CHRONOS_GEMM_PLAN: another file) read once, section -> {(N, K, epilogue):
+# rows sorted by M}.  ``_plan_cache`` holds the answers of the plan functions, keyed by every switch they depend on.
+# ``_plan_table = None`` (or ``_reset_plans()``) makes the next lookup read the file again.
+_PLAN_SECTIONS = ("plans", "qplans", "w4plans", "w4mplans")
 _plan_table: Optional[dict] = None
-_qplan_table: Optional[dict] = None
-_w4plan_table: Optional[dict] = None
-_w4mplan_table: Optional[dict] = None
+_plan_cache: dict = {}
 
 
-def _plan_file() -> dict:
-    global _plan_table, _qplan_table, _w4plan_table, _w4mplan_table
+def _load_plans() -> dict:
+    global _plan_table
     if _plan_table is None:
         import json
 
@@ -121,11 +123,27 @@ def _plan_file() -> dict:
                 raise FileNotFoundError(f"CHRONOS_GEMM_PLAN={override!r}: no such plan file") from None
             raw = {}
         key = lambda k: tuple(int(v) for v in k.split(","))  # noqa: E731
-        _plan_table = {key(k): rows for k, rows in raw.get("plans", {}).items()}
-        _qplan_table = {key(k): rows for k, rows in raw.get("qplans", {}).items()}
-        _w4plan_table = {key(k): rows for k, rows in raw.get("w4plans", {}).items()}
-        _w4mplan_table = {key(k): rows for k, rows in raw.get("w4mplans", {}).items()}
+        _plan_table = {sec: {key(k): rows for k, rows in raw.get(sec, {}).items()} for sec in _PLAN_SECTIONS}
     return _plan_table
+
+
+def _reset_plans(**sections) -> None:
+    """Forget the plan file and every cached answer; the next lookup reads the file again.  With sections given
+    (``plans=``, ``qplans=``, ``w4plans=``, ``w4mplans=``: tables keyed like the loaded ones) these stand in for the
+    file, the others empty: the tests' way to inject rows."""
+    global _plan_table
+    assert set(sections) <= set(_PLAN_SECTIONS), sections
+    _plan_table = {sec: sections.get(sec, {}) for sec in _PLAN_SECTIONS} if sections else None
+    _plan_cache.clear()
+
+
+def _plan_row(section: str, key: tuple, m: int, last_covers_above: bool = True):
+    """The row of a shape that decides M: rows [measured M, ...] sorted by M, a measured M decides (previous M, M].
+    Above the last row: that row, or (``last_covers_above`` False, "w4mplans") None = not measured.  No rows: None."""
+    rows = _load_plans()[section].get(key)
+    if not rows:
+        return None
+    return next((r for r in rows if m <= r[0]), rows[-1] if last_covers_above else None)
 
 
 QLG_BASE = 10  # qplan code >= QLG_BASE: gemm_lg.hip's fp8 config (code - QLG_BASE), row [M, code, split-K]
@@ -137,11 +155,9 @@ def qplan_route(m: int, n: int, k: int, swiglu: bool) -> Optional[tuple[int, int
     """W8A8 fp8 projection route from ops/gemm_plan.json "qplans" (``scripts/tune_gemm_pp.py --fp8``), rows
     [measured M, code(, split-K)] per (N, K, swiglu) read like the bf16 plan's: code 0 = the library's fp8 GEMM, 1 =
     fp8.hip (qgemv / block-scaled MFMA qgemm), QLG_BASE + c = gemm_lg.hip fp8 config c.  None = not measured."""
-    _plan_file()
-    rows = (_qplan_table or {}).get((n, k, int(swiglu)))
-    if not rows:
+    pick = _plan_row("qplans", (n, k, int(swiglu)), m)
+    if pick is None:
         return None
-    pick = next((r for r in rows if m <= r[0]), rows[-1])
     return int(pick[1]), int(pick[2]) if len(pick) > 2 else 1
 
 
@@ -151,11 +167,16 @@ def qplan_own(m: int, n: int, k: int, swiglu: bool) -> Optional[bool]:
     return None if r is None else r[0] != 0
 
 
-def _sk_valid(c: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
-    rt, mt, nw = _SK[c]
-    if m > 16 * mt or k % (64 * nw * sk):
+def _skinny_valid(cfg: tuple, unit: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
+    """gemm_skinny.hip's shape rules for a (RT, MT, NW) config whose K unit is ``unit`` (bf16: 64, W4A16: 128)."""
+    rt, mt, nw = cfg
+    if m > 16 * mt or k % (unit * nw * sk):
         return False
     return (rt % 2 == 0 and n % 2 == 0 and (n // 2) % (8 * rt) == 0) if mode == PP_SWIGLU else n % (16 * rt) == 0
+
+
+def _sk_valid(c: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
+    return _skinny_valid(_SK[c], 64, m, n, k, mode, sk)
 
 
 def _sk_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tuple[int, int]]:
@@ -181,10 +202,7 @@ def _sk4_valid(c: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
     """The binding's rules for the W4A16 skinny mode (bindings.cpp gemm_skinny with ``we``)."""
     if c not in _SK4 or sk < 1 or m < 1 or k < 1 or k > (1 << 20):
         return False
-    rt, mt, nw = _SK4[c]
-    if m > 16 * mt or k % (128 * nw * sk):
-        return False
-    return (rt % 2 == 0 and n % 2 == 0 and (n // 2) % (8 * rt) == 0) if mode == PP_SWIGLU else n % (16 * rt) == 0
+    return _skinny_valid(_SK4[c], 128, m, n, k, mode, sk)
 
 
 def _sk4_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tuple[int, int]]:
@@ -213,13 +231,9 @@ def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) 
     a full write and re-read of the weight matrix in front of the bf16 kernel — so every shape the kernel accepts takes
     it: the plan's winning row where there is one, the ``_sk4_model`` pick for a shape without a row and for a row the
     copy won (by at most 13 %, QKV / gate_up at M = 40-64; scripts/bench_w4_expand.py measures those points)."""
-    global _w4_skinny_seen
-    if W4_SKINNY != _w4_skinny_seen:
-        _plan_cache.clear()
-        _w4_skinny_seen = W4_SKINNY
     if not _W4A16_DECODE or W4_SKINNY == "off" or m < 1 or m > W4_SKINNY_MAX_M:
         return None
-    key = ("w4p" if packed else "w4", m, n, k, mode)
+    key = ("w4", W4_SKINNY, packed, m, n, k, mode)
     hit = _plan_cache.get(key, False)
     if hit is not False:
         return hit
@@ -227,11 +241,9 @@ def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) 
     if W4_SKINNY == "model":
         out = _sk4_model(m, n, k, mode)
     else:
-        _plan_file()
-        rows = (_w4plan_table or {}).get((n, k, mode))
-        if rows:
-            pick = next((r for r in rows if m <= r[0]), rows[-1])
-            out = None if pick[1] < 0 else (int(pick[1]), int(pick[2]))
+        pick = _plan_row("w4plans", (n, k, mode), m)
+        if pick is not None and pick[1] >= 0:
+            out = (int(pick[1]), int(pick[2]))
         if packed and (out is None or not _sk4_valid(out[0], m, n, k, mode, out[1])):
             out = _sk4_model(m, n, k, mode)
     if out is not None and not _sk4_valid(out[0], m, n, k, mode, out[1]):
@@ -271,13 +283,9 @@ def _w4m_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tu
 def w4m_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) -> Optional[tuple[int, int]]:
     """(config, split-K) of the mid-M W4A16 GEMM (gemm_w4m.hip) for a Q4Tensor projection at this shape, or None for
     the bf16 route (the copy, or the expansion when ``packed``).  See ``W4_MID`` above for the plan's semantics."""
-    global _w4_mid_seen
-    if W4_MID != _w4_mid_seen:
-        _plan_cache.clear()
-        _w4_mid_seen = W4_MID
     if not _W4A16_DECODE or W4_MID == "off" or m < W4M_MIN_M or m > W4M_MAX_M:
         return None
-    key = ("w4mp" if packed else "w4m", m, n, k, mode)
+    key = ("w4m", W4_MID, packed, m, n, k, mode)
     hit = _plan_cache.get(key, False)
     if hit is not False:
         return hit
@@ -285,12 +293,9 @@ def w4m_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False)
     if W4_MID == "model":
         out = _w4m_model(m, n, k, mode)
     else:
-        _plan_file()
-        rows = (_w4mplan_table or {}).get((n, k, mode))
-        if rows:
-            pick = next((r for r in rows if m <= r[0]), None)  # no row at or above M: not measured
-            if pick is not None and pick[1] >= 0 and (pick[3] >= 2 or (pick[3] == 1 and packed)):
-                out = (int(pick[1]), int(pick[2]))
+        pick = _plan_row("w4mplans", (n, k, mode), m, last_covers_above=False)  # no row at or above M: not measured
+        if pick is not None and pick[1] >= 0 and (pick[3] >= 2 or (pick[3] == 1 and packed)):
+            out = (int(pick[1]), int(pick[2]))
     if out is not None and not _w4m_valid(out[0], m, n, k, mode, out[1]):
         out = None
     _plan_cache[key] = out
@@ -328,20 +333,20 @@ def pp_plan(m: int, n: int, k: int, mode: int = PP_PLAIN) -> Optional[tuple[int,
     or None for the library."""
     if m <= GEMV_MAX_M or PP_MODE == "lib":
         return None
-    key = (m, n, k, mode)
+    key = ("pp", PP_MODE, m, n, k, mode)
     hit = _plan_cache.get(key, False)
     if hit is not False:
         return hit
     out = None
     if k % 64 == 0 and (n % 4 == 0 if mode == PP_PLAIN else n % 128 == 0):
-        rows = _plan_file().get((n, k, mode))
         if PP_MODE == "own":
             out = (_sk_model(m, n, k, mode) if m <= SKINNY_MAX_M else None) or _pp_model(m, n, k, mode)
-        elif rows:
-            # rows [measured M, cfg, split-K] sorted by M: a measured M decides (previous M, M]; the last row also
-            # everything above it.  cfg < 0 = the library measured faster.
-            pick = next((r for r in rows if m <= r[0]), rows[-1])
-            out = None if pick[1] < 0 else (pick[1], pick[2])
+        else:
+            # rows [measured M, cfg, split-K]: the last row also decides everything above it.  cfg < 0 = the library
+            # measured faster.
+            pick = _plan_row("plans", (n, k, mode), m)
+            if pick is not None and pick[1] >= 0:
+                out = (pick[1], pick[2])
         # auto, shape never measured: the library (a hand-written config is routed only on a recorded A/B)
         if out is not None and not _pp_valid(out[0], n, k, mode, out[1], m):
             out = None
@@ -360,13 +365,6 @@ def pp_gemm(x: torch.Tensor, w: torch.Tensor, mode: int, plan: tuple[int, int], 
         return _k().gemm_skinny(x.reshape(-1, k), w, mode, plan[0] - SK_BASE, plan[1], resid, part, eps)
     y, pt = _k().gemm_pp(x.reshape(-1, k), w, mode, plan[0], plan[1], resid, part, eps, False)
     return y, pt
-
-# (M, N, K) -> bool predicate + kernel; extension point for further shape-specialised kernels
-_custom: list[tuple[Callable[[int, int, int], bool], Callable[[torch.Tensor, torch.Tensor], torch.Tensor]]] = []
-
-
-def register(pred: Callable[[int, int, int], bool], fn: Callable[[torch.Tensor, torch.Tensor], torch.Tensor]) -> None:
-    _custom.append((pred, fn))
 
 
 @dataclass
@@ -521,54 +519,41 @@ def gemv_w4_ok(m: int, n: int, k: int) -> bool:
 
 
 def _w4_route(t: torch.Tensor, m: int, n: int, k: int, mmax: int = 4) -> bool:
-    """True: the fp4 kernel takes this call (and is counted); False: the caller substitutes ``w.w``."""
-    if not (_W4A16_DECODE and t.is_cuda and m <= min(mmax, W4_MAX_M) and gemv_w4_ok(m, n, k)):
-        return False
-    w4_stats["gemv_launches"] += 1
-    return True
+    """True: the fp4 GEMV takes this call (the caller launches it and counts it in ``w4_stats``); False: the caller
+    goes on down the ladder."""
+    return bool(_W4A16_DECODE and t.is_cuda and m <= min(mmax, W4_MAX_M) and gemv_w4_ok(m, n, k))
 
 
-def _w4_skinny(x, w, mode: int, m: int, resid=None):
-    """The W4A16 skinny launch for a Q4Tensor call the GEMV did not take: (y, partials), or None when ``w4_plan`` has
-    no route (the caller substitutes ``w.w``).  A fusable LazyNorm goes in as the kernel's NORMP prologue."""
-    lazy = isinstance(x, LazyNorm)
-    t = x.s if lazy else x
-    if not t.is_cuda:
+def decode_gemv_weight(t: torch.Tensor, w, m: int, n: int, k: int):
+    """What a fused decode GEMV epilogue (``ops.qkv_rope``, M <= 2) streams for this projection weight: (weight, fp8 row
+    scales or None, mxfp4 block scales or None), or None off the GEMV's shapes.  A Q4Tensor off the fp4 GEMV's shapes
+    goes in as ``w4_dense`` — asked only once the bf16 GEMV takes the call: no expansion for a call that is not made."""
+    if is_w4(w):
+        if _w4_route(t, m, n, k, 2):
+            return w.q, None, w.e
+        return (w4_dense(w), None, None) if t.is_cuda and m <= 2 and gemv_ok(m, n, k) else None
+    if not (t.is_cuda and m <= 2):
         return None
-    k = t.shape[-1]
-    plan = w4_plan(m, w.shape[0], k, mode, w.w is None)
+    if is_q(w):
+        return (w.q, w.s, None) if gemv_q_ok(m, n, k) else None
+    return (w, None, None) if gemv_ok(m, n, k) else None
+
+
+def _w4_gemm(x, w, mode: int, m: int, n: int, k: int, fuse: bool, resid=None):
+    """The W4A16 MFMA launch for a Q4Tensor call the GEMV did not take — the skinny kernel up to W4_SKINNY_MAX_M rows,
+    the mid-M GEMM (gemm_w4m.hip) above: (y, partials), or None when ``w4_plan`` / ``w4m_plan`` has no route (the
+    caller substitutes ``w4_dense``).  ``fuse``: x is a fusable LazyNorm and goes in as the kernel's NORMP prologue."""
+    mid = m > W4_SKINNY_MAX_M
+    plan = (w4m_plan if mid else w4_plan)(m, n, k, mode, w.w is None)
     if plan is None:
         return None
     from . import _k
 
-    w4_stats["skinny_launches"] += 1
-    if lazy and x.fusable() and mode != PP_RESID:
-        return _k().gemm_skinny(x.s.reshape(-1, k), w.q, mode, plan[0], plan[1], None, x.part, x.eps, w.e)
-    x = LazyNorm.force(x)
-    return _k().gemm_skinny(x.reshape(-1, k), w.q, mode, plan[0], plan[1], resid, None, 1e-5, w.e)
-
-
-def _w4_mid(x, w, mode: int, m: int, resid=None):
-    """The mid-M W4A16 launch (gemm_w4m.hip) for a Q4Tensor call neither the GEMV nor the skinny kernel took: (y,
-    partials), or None when ``w4m_plan`` has no route (the caller substitutes ``w4_dense``).  A fusable LazyNorm goes in
-    as the kernel's NORMP prologue."""
-    if m < W4M_MIN_M or m > W4M_MAX_M:
-        return None
-    lazy = isinstance(x, LazyNorm)
-    t = x.s if lazy else x
-    if not t.is_cuda:
-        return None
-    k = t.shape[-1]
-    plan = w4m_plan(m, w.shape[0], k, mode, w.w is None)
-    if plan is None:
-        return None
-    from . import _k
-
-    w4_stats["mid_launches"] += 1
-    if lazy and x.fusable() and mode != PP_RESID:
-        return _k().gemm_w4m(x.s.reshape(-1, k), w.q, w.e, mode, plan[0], plan[1], None, x.part, x.eps)
-    x = LazyNorm.force(x)
-    return _k().gemm_w4m(x.reshape(-1, k), w.q, w.e, mode, plan[0], plan[1], resid, None, 1e-5)
+    w4_stats["mid_launches" if mid else "skinny_launches"] += 1
+    t, resid, part, eps = (x.s, None, x.part, x.eps) if fuse else (LazyNorm.force(x), resid, None, 1e-5)
+    if mid:
+        return _k().gemm_w4m(t.reshape(-1, k), w.q, w.e, mode, plan[0], plan[1], resid, part, eps)
+    return _k().gemm_skinny(t.reshape(-1, k), w.q, mode, plan[0], plan[1], resid, part, eps, w.e)
 
 
 def _q_fallback(x, w, swiglu: bool = False) -> torch.Tensor:
@@ -580,36 +565,19 @@ def _q_fallback(x, w, swiglu: bool = False) -> torch.Tensor:
     return y.view(*x.shape[:-1], y.shape[-1])
 
 
-def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOut:
-    """Producer (O / down projection, TP=1): the new residual stream s = bf16(bf16(x @ w.T) + resid) and the RMSNorm
-    partial sums of s^2, in one launch — the GEMV at M <= 2, the batched GEMM's kResid epilogue above.  ``w`` may be
-    an fp8 QTensor at the W8A16 GEMV shapes (resid_ok(..., fp8=True))."""
+def _gemv_resid(x, w: torch.Tensor, resid: torch.Tensor, ws=None, we=None) -> ResidOut:
+    """The decode GEMV's residual producer (gemv.hip kResid) on bf16 weights, fp8 bytes (``ws``) or mxfp4 (``we``)."""
     from . import _k
 
-    m, k = x.numel() // x.shape[-1], x.shape[-1]
-    if is_w4(w):
-        # the fp4 producer at the W8A16 precedent's rows (M <= min(GEMV_MAX_M, 2)); 8 rows per group: N / 8 partials,
-        # which the consumer reads as float4
-        if w.shape[0] % 32 == 0 and _w4_route(x, m, w.shape[0], k, min(GEMV_MAX_M, 2)):
-            s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
-            part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, None, w.e)
-            return ResidOut(s, part)
-        hit = _w4_skinny(x, w, PP_RESID, m, resid.reshape(m, -1))
-        if hit is None:
-            hit = _w4_mid(x, w, PP_RESID, m, resid.reshape(m, -1))
-        if hit is not None:
-            return ResidOut(hit[0].view(resid.shape), hit[1])
-        w = w4_dense(w)
-    if is_q(w):
-        s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
-        part = _k().gemv_resid(x.reshape(-1, k), w.q, resid, s, w.s)
-        return ResidOut(s, part)
-    if m > GEMV_MAX_M:
-        s, part = pp_gemm(x, w, PP_RESID, pp_plan(m, w.shape[0], k, PP_RESID), resid.reshape(m, -1))
-        return ResidOut(s.view(resid.shape), part)
     s = torch.empty(resid.shape, dtype=resid.dtype, device=resid.device)
-    part = _k().gemv_resid(x.reshape(-1, x.shape[-1]), w, resid, s)
-    return ResidOut(s, part)
+    return ResidOut(s, _k().gemv_resid(x.reshape(-1, x.shape[-1]), w, resid, s, ws, we))
+
+
+def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOut:
+    """Producer (O / down projection, TP=1): the new residual stream s = bf16(bf16(x @ w.T) + resid) and the RMSNorm
+    partial sums of s^2, in one launch — the GEMV at M <= GEMV_MAX_M, the batched GEMM's kResid epilogue above.  ``w``
+    may be an fp8 QTensor at the W8A16 GEMV shapes (resid_ok(..., fp8=True)).  Only where ``resid_ok`` says so."""
+    return _project(x, w, PP_RESID, resid)
 
 
 def resid_ok(m: int, n: int, k: int, fp8: bool = False) -> bool:
@@ -637,11 +605,15 @@ def mfma_swiglu_ok(m: int, n: int, k: int) -> bool:
     return 3 <= m <= 128 and k % 64 == 0 and n % 128 == 0
 
 
-def _gemv(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> torch.Tensor:
+def _gemv(x, w: torch.Tensor, swiglu: bool = False, ws=None, we=None, fuse: bool = False) -> torch.Tensor:
+    """The decode GEMV on bf16 weights, fp8 bytes (``ws``: row scales) or mxfp4 (``we``: block scales).  ``fuse``: x is
+    a fusable LazyNorm and its norm the kernel's per-row output scale (gemv.hip NORMP); otherwise x is materialised."""
     from . import _k
 
-    k = x.shape[-1]
-    y = _k().gemv(x.reshape(-1, k), w, swiglu)
+    if fuse:
+        return _k().gemv_normp(x.s, x.part, x.eps, w, swiglu, ws, we)
+    x = LazyNorm.force(x)
+    y = _k().gemv(x.reshape(-1, x.shape[-1]), w, swiglu, ws, we)
     return y.view(*x.shape[:-1], y.shape[-1])
 
 
@@ -653,111 +625,72 @@ def mfma_gemm(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, stages: in
     return y.view(*x.shape[:-1], y.shape[-1])
 
 
-def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
-    """silu(x @ gate.T) * (x @ up.T) with w_gu = [gate; up]: one fused launch (GEMV at M <= 2, the batched GEMM's
-    SwiGLU epilogue above, with the folded input norm when x is a LazyNorm), else GEMM + silu_mul."""
-    from . import _k, silu_mul
+def _project(x, w, mode: int, resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """The one dispatcher behind ``linear`` (PP_PLAIN), ``gate_up_silu`` (PP_SWIGLU) and ``gemv_resid`` (PP_RESID, with
+    ``resid``): the ladder of the module docstring, walked once.  ``out`` (linear only) keeps the call off every
+    Q4Tensor kernel, every fused norm and every planned GEMM: it is the library's ``out=``.  (The plain decode GEMV and
+    the fp8 paths do not look at it and return a new tensor, as they always did.)"""
+    lazy = isinstance(x, LazyNorm)
+    t = x.s if lazy else x
+    k = t.shape[-1]
+    m, n = t.numel() // k, w.shape[0]
+    swiglu = mode == PP_SWIGLU
+    fuse = lazy and x.fusable() and mode != PP_RESID  # the folded norm can go in as the kernel's prologue
 
-    if is_w4(w_gu):  # mxfp4 weights: the W4A16 GEMV at its shapes, else the bf16 copy through the code below
-        lazy = isinstance(x, LazyNorm)
-        t = x.s if lazy else x
-        m, n, k = t.numel() // t.shape[-1], w_gu.shape[0], t.shape[-1]
-        if _w4_route(t, m, n, k):
-            if lazy and x.fusable() and m <= 2:
-                return _k().gemv_normp(x.s, x.part, x.eps, w_gu.q, True, None, w_gu.e)
-            x = LazyNorm.force(x)
-            y = _k().gemv(x.reshape(-1, k), w_gu.q, True, None, w_gu.e)
-            return y.view(*x.shape[:-1], y.shape[-1])
-        hit = _w4_skinny(x, w_gu, PP_SWIGLU, m)
-        if hit is None:
-            hit = _w4_mid(x, w_gu, PP_SWIGLU, m)
-        if hit is not None:
-            return hit[0].view(*x.shape[:-1], n // 2)
-        w_gu = w4_dense(w_gu)
-    if is_q(w_gu):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
-        m, n, k = (x.rows() if isinstance(x, LazyNorm) else x.numel() // x.shape[-1]), w_gu.shape[0], x.shape[-1]
-        if isinstance(x, LazyNorm) and x.fusable() and m <= 2 and gemv_q_ok(m, n, k):
-            return _k().gemv_normp(x.s, x.part, x.eps, w_gu.q, True, w_gu.s)
-        x = LazyNorm.force(x)
-        if x.is_cuda and gemv_q_ok(m, n, k):
-            y = _k().gemv(x.reshape(-1, k), w_gu.q, True, w_gu.s)
-            return y.view(*x.shape[:-1], y.shape[-1])
-        return _q_fallback(x, w_gu, True)
-    if isinstance(x, LazyNorm):
-        m, n, k = x.rows(), w_gu.shape[0], x.shape[-1]
-        if x.fusable() and gemv_ok(m, n, k, swiglu=True):
-            return _k().gemv_normp(x.s, x.part, x.eps, w_gu, True)
-        plan = pp_plan(m, n, k, PP_SWIGLU) if x.fusable() else None
-        if plan is not None:
-            y, _ = pp_gemm(x.s, w_gu, PP_SWIGLU, plan, None, x.part, x.eps)
-            return y.view(*x.shape[:-1], n // 2)
-        x = x.materialize()
-    if x.is_cuda:
-        m, n, k = x.numel() // x.shape[-1], w_gu.shape[0], x.shape[-1]
-        if gemv_ok(m, n, k, swiglu=True):
-            return _gemv(x, w_gu, True)
-        plan = pp_plan(m, n, k, PP_SWIGLU)
-        if plan is not None:
-            y, _ = pp_gemm(x, w_gu, PP_SWIGLU, plan)
-            return y.view(*x.shape[:-1], n // 2)
-        if mfma_swiglu_ok(m, n, k):
-            return mfma_gemm(x, w_gu, True)
-    return silu_mul(linear(x, w_gu))
+    def shaped(y, part=None):
+        return ResidOut(y.view(resid.shape), part) if mode == PP_RESID else y.view(*t.shape[:-1], y.shape[-1])
 
-
-def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    if is_w4(w):  # mxfp4 weights: the W4A16 GEMV at its shapes, else the bf16 copy through the code below
-        lazy = isinstance(x, LazyNorm)
-        t = x.s if lazy else x
-        m, n, k = t.numel() // t.shape[-1], w.shape[0], t.shape[-1]
-        if out is None and _w4_route(t, m, n, k):
-            from . import _k
-
-            if lazy and x.fusable() and m <= 2:
-                return _k().gemv_normp(x.s, x.part, x.eps, w.q, False, None, w.e)
-            x = LazyNorm.force(x)
-            y = _k().gemv(x.reshape(-1, k), w.q, False, None, w.e)
-            return y.view(*x.shape[:-1], n)
-        hit = _w4_skinny(x, w, PP_PLAIN, m) if out is None else None
-        if hit is None and out is None:
-            hit = _w4_mid(x, w, PP_PLAIN, m)
-        if hit is not None:
-            return hit[0].view(*x.shape[:-1], n)
+    if is_w4(w):  # mxfp4 weights: a W4A16 kernel where one is routed, else the bf16 steps on the dense form
+        if t.is_cuda and out is None:
+            # the fp4 residual producer at the W8A16 precedent's rows (M <= min(GEMV_MAX_M, 2)); 8 rows per group: N / 8
+            # partials, which the consumer reads as float4
+            cap, nmul = (min(GEMV_MAX_M, 2), 32) if mode == PP_RESID else (4, 16)
+            if n % nmul == 0 and _w4_route(t, m, n, k, cap):
+                w4_stats["gemv_launches"] += 1
+                if mode == PP_RESID:
+                    return _gemv_resid(x, w.q, resid, None, w.e)
+                return _gemv(x, w.q, swiglu, None, w.e, fuse and m <= 2)
+            hit = _w4_gemm(x, w, mode, m, n, k, fuse, resid.reshape(m, -1) if mode == PP_RESID else None)
+            if hit is not None:
+                return shaped(*hit)
         w = w4_dense(w)
-    if is_q(w):  # fp8 weights: the W8A16 GEMV (folded norm fused when x is a LazyNorm), else W8A8
-        from . import _k
-
-        m, n, k = (x.rows() if isinstance(x, LazyNorm) else x.numel() // x.shape[-1]), w.shape[0], x.shape[-1]
-        if isinstance(x, LazyNorm) and x.fusable() and m <= 2 and gemv_q_ok(m, n, k):
-            return _k().gemv_normp(x.s, x.part, x.eps, w.q, False, w.s)
-        x = LazyNorm.force(x)
-        if x.is_cuda and gemv_q_ok(m, n, k):
-            y = _k().gemv(x.reshape(-1, k), w.q, False, w.s)
-            return y.view(*x.shape[:-1], n)
-        return _q_fallback(x, w)
-    if isinstance(x, LazyNorm):
-        m, n, k = x.rows(), w.shape[0], x.shape[-1]
-        if x.fusable() and out is None and gemv_ok(m, n, k):
-            from . import _k
-
-            return _k().gemv_normp(x.s, x.part, x.eps, w, False)
-        plan = pp_plan(m, n, k, PP_PLAIN) if x.fusable() and out is None else None
+    if is_q(w):  # fp8 weights: the W8A16 GEMV (folded norm fused at M <= 2 when x is a LazyNorm), else W8A8
+        if mode == PP_RESID:
+            return _gemv_resid(x, w.q, resid, w.s)
+        if t.is_cuda and gemv_q_ok(m, n, k):
+            return _gemv(x, w.q, swiglu, w.s, None, fuse and m <= 2)
+        return _q_fallback(LazyNorm.force(x), w, swiglu)
+    if mode == PP_RESID:
+        if m > GEMV_MAX_M:
+            return shaped(*pp_gemm(x, w, PP_RESID, pp_plan(m, n, k, PP_RESID), resid.reshape(m, -1)))
+        return _gemv_resid(x, w, resid)
+    if t.is_cuda:
+        if gemv_ok(m, n, k, swiglu):
+            return _gemv(x, w, swiglu, fuse=fuse and out is None)
+        plan = pp_plan(m, n, k, mode) if out is None else None
         if plan is not None:
-            y, _ = pp_gemm(x.s, w, PP_PLAIN, plan, None, x.part, x.eps)
-            return y.view(*x.shape[:-1], n)
-        x = x.materialize()
-    if x.is_cuda:
-        m, k = x.numel() // x.shape[-1], x.shape[-1]
-        n = w.shape[0]
-        if gemv_ok(m, n, k):
-            return _gemv(x, w)
-        for pred, fn in _custom:
-            if pred(m, n, k):
-                return fn(x, w)
-        plan = pp_plan(m, n, k, PP_PLAIN) if out is None else None
-        if plan is not None:
-            y, _ = pp_gemm(x, w, PP_PLAIN, plan)
-            return y.view(*x.shape[:-1], n)
+            if fuse:
+                y, _ = pp_gemm(x.s, w, mode, plan, None, x.part, x.eps)
+            else:
+                y, _ = pp_gemm(LazyNorm.force(x), w, mode, plan)
+            return shaped(y)
+    x = LazyNorm.force(x)
+    if swiglu:
+        if x.is_cuda and mfma_swiglu_ok(m, n, k):
+            return mfma_gemm(x, w, True)
+        from . import silu_mul
+
+        return silu_mul(_project(x, w, PP_PLAIN))
     if out is not None:
         return torch.matmul(x, w.t(), out=out)
     return torch.matmul(x, w.t())
+
+
+def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
+    """silu(x @ gate.T) * (x @ up.T) with w_gu = [gate; up]: one fused launch (GEMV at M <= GEMV_MAX_M, the batched
+    GEMM's SwiGLU epilogue above, with the folded input norm when x is a LazyNorm), else GEMM + silu_mul."""
+    return _project(x, w_gu, PP_SWIGLU)
+
+
+def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return _project(x, w, PP_PLAIN, out=out)

@@ -6,12 +6,18 @@ import pytest
 from chronos.ops import gemm as G
 
 
+@pytest.fixture(autouse=True)
+def _plan_file_afterwards():
+    """Whatever a test injected with ``G._reset_plans(...)`` is forgotten again: the next lookup reads the file."""
+    yield
+    G._reset_plans()
+
+
 @pytest.fixture
 def plan(monkeypatch):
     table = {(4096, 4096, 2): [[5, 101, 2], [64, 106, 8], [256, 1, 2], [1024, -1, 1], [4096, 0, 1]],
              (6144, 4096, 0): [[8, 100, 3]]}  # split 3 does not divide 4096 / 1024: invalid -> library
-    monkeypatch.setattr(G, "_plan_table", table)
-    monkeypatch.setattr(G, "_plan_cache", {})
+    G._reset_plans(plans=table)
     monkeypatch.setattr(G, "PP_MODE", "auto")
     return table
 
@@ -32,8 +38,7 @@ def test_plan_rows_by_m(plan):
 
 
 def test_skinny_row_beyond_its_m_bound_is_rejected(monkeypatch):
-    monkeypatch.setattr(G, "_plan_table", {(4096, 4096, 0): [[64, 100, 1]]})  # cfg 0: M <= 16 only
-    monkeypatch.setattr(G, "_plan_cache", {})
+    G._reset_plans(plans={(4096, 4096, 0): [[64, 100, 1]]})  # cfg 0: M <= 16 only
     monkeypatch.setattr(G, "PP_MODE", "auto")
     assert G.pp_plan(16, 4096, 4096, 0) == (100, 1)
     assert G.pp_plan(17, 4096, 4096, 0) is None
@@ -57,15 +62,13 @@ def test_skinny_model_valid(m, n, k, mode):
 
 
 def test_own_mode_uses_skinny_then_tiles(monkeypatch):
-    monkeypatch.setattr(G, "_plan_cache", {})
     monkeypatch.setattr(G, "PP_MODE", "own")
     assert G.pp_plan(5, 4096, 4096, G.PP_PLAIN)[0] >= G.SK_BASE
     assert G.pp_plan(512, 4096, 4096, G.PP_PLAIN)[0] < G.SK_BASE
 
 
 def test_fp8_qplan(monkeypatch):
-    monkeypatch.setattr(G, "_plan_table", {})
-    monkeypatch.setattr(G, "_qplan_table", {(28672, 4096, 1): [[4, 1], [128, 1], [1024, 0], [16384, 1]]})
+    G._reset_plans(plans={}, qplans={(28672, 4096, 1): [[4, 1], [128, 1], [1024, 0], [16384, 1]]})
     assert G.qplan_own(3, 28672, 4096, True) is True
     assert G.qplan_own(512, 28672, 4096, True) is False
     assert G.qplan_own(20000, 28672, 4096, True) is True

@@ -125,16 +125,14 @@ def gemm():
         yield g
     finally:
         g.W4_MID, g.W4_SKINNY, g._W4A16_DECODE = old
-        g._plan_table = g._qplan_table = g._w4plan_table = g._w4mplan_table = None
-        g._plan_cache.clear()
+        g._reset_plans()
 
 
 def _load(gemm, monkeypatch, tmp_path, raw):
     path = tmp_path / "plan.json"
     path.write_text(json.dumps(raw))
     monkeypatch.setenv("CHRONOS_GEMM_PLAN", str(path))
-    gemm._plan_table = gemm._qplan_table = gemm._w4plan_table = gemm._w4mplan_table = None
-    gemm._plan_cache.clear()
+    gemm._reset_plans()
 
 
 def test_w4mplans_section(gemm, monkeypatch, tmp_path):

@@ -454,7 +454,7 @@ def test_beats_one_rows_route_packed_tensors_only(switch, monkeypatch, tmp_path)
     path = tmp_path / "plan.json"
     path.write_text(json.dumps({"w4mplans": {f"{n},{k},0": [[128, 0, 2, 1]], f"{n},{k},1": [[128, 0, 1, 2]]}}))
     monkeypatch.setenv("CHRONOS_GEMM_PLAN", str(path))
-    reset = lambda: (setattr(gemm, "_plan_table", None), gemm._plan_cache.clear())  # noqa: E731
+    reset = gemm._reset_plans
     reset()
     try:
         switch("plan")

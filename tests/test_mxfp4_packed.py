@@ -177,10 +177,10 @@ def test_w4_plan_packed_takes_the_kernel_where_copy_mode_takes_the_copy():
     assert gemm.W4_SKINNY == "plan" and gemm._W4A16_DECODE
     norow = (1024, 1024, gemm.PP_PLAIN)                       # never measured: no "w4plans" row
     lost = [(6144, 4096, gemm.PP_PLAIN), (28672, 4096, gemm.PP_SWIGLU)]  # rows whose M = 40-64 entries are -1
-    gemm._plan_file()
-    assert norow not in gemm._w4plan_table
+    w4plans = gemm._load_plans()["w4plans"]
+    assert norow not in w4plans
     for n, k, mode in lost:
-        assert gemm._w4plan_table[(n, k, mode)][-1][:2] == [64, -1]
+        assert w4plans[(n, k, mode)][-1][:2] == [64, -1]
     for m in (2, 40, 48, 64):
         assert gemm.w4_plan(m, *norow) is None
         got = gemm.w4_plan(m, *norow, packed=True)
