@@ -67,6 +67,13 @@ int gemm_skinny_w4_rt(int cfg);
 int gemm_skinny_w4_mt(int cfg);
 int gemm_skinny_w4_nw(int cfg);
 bool launch_gemm_skinny_w4(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st);
+// ... and its W8A16 weight mode (a.w = e4m3fn bytes [N, K], a.wsc = f32 per-output-row scales [N], applied to the
+// summed f32 result in front of every epilogue), own config ids: M <= 16 * MT <= 64, K % (64 * NW * splitk) == 0
+constexpr int kSkinnyW8Configs = 12;
+int gemm_skinny_w8_rt(int cfg);
+int gemm_skinny_w8_mt(int cfg);
+int gemm_skinny_w8_nw(int cfg);
+bool launch_gemm_skinny_w8(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st);
 
 // mid-M W4A16 family (csrc/kernels/gemm_w4m.hip, any M; routed for 65 <= M <= 512): a.w = packed e2m1 [N, K / 2],
 // a.wexp = e8m0 [N, K / 32], same epilogues; 4 waves, tile = WN W rows x XM x rows, x through an LDS ring of ST

@@ -854,14 +854,28 @@ std::tuple<Tensor, Tensor> gemm_pp(const Tensor& x, const Tensor& w, int64_t mod
 }
 
 // Skinny-M GEMM (gemm_skinny.hip), M <= 16 * MT of the config: the kResid partials are [M, N / (16 * RT)].  With ``we``
-// the W4A16 weight mode: w / we = mxfp4 q / e, cfg an id of the W4 config table, K % (128 * NW * splitk) == 0.
+// the W4A16 weight mode: w / we = mxfp4 q / e, cfg an id of the W4 config table, K % (128 * NW * splitk) == 0.  With
+// ``wscale`` (and no ``we``) the W8A16 weight mode: w = e4m3fn bytes [N, K], wscale = f32 per-row scales [N], cfg an id
+// of the W8 config table, K % (64 * NW * splitk) == 0.
 std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t mode, int64_t cfg, int64_t splitk,
                                        const c10::optional<Tensor>& resid, const c10::optional<Tensor>& part_in,
-                                       double eps, const c10::optional<Tensor>& we) {
+                                       double eps, const c10::optional<Tensor>& we,
+                                       const c10::optional<Tensor>& wscale) {
     chk_gemm_x("gemm_skinny", x, mode, part_in);
-    const bool w4 = we.has_value();
+    const bool w4 = we.has_value(), w8 = wscale.has_value();
+    CHK(!(w4 && w8), "gemm_skinny: wscale (W8A16) and we (W4A16) exclude each other");
     const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0);
-    if (w4) {
+    if (w8) {
+        chk_gpu(w, "w");
+        chk_gpu(*wscale, "wscale");
+        CHK(w.scalar_type() == at::kByte && w.dim() == 2 && w.size(1) == K && w.is_contiguous() &&
+                reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+            "gemm_skinny: W8 w must be contiguous uint8 [N, K], 16-B aligned");
+        CHK(wscale->scalar_type() == at::kFloat && wscale->dim() == 1 && wscale->size(0) == N && wscale->is_contiguous(),
+            "gemm_skinny: wscale must be contiguous f32 [N]");
+        CHK(w.device() == x.device() && wscale->device() == x.device(), "gemm_skinny: w / wscale on x's device");
+        CHK(cfg >= 0 && cfg < chronos::kSkinnyW8Configs, "gemm_skinny: W8 cfg");
+    } else if (w4) {
         chk_mxfp4("gemm_skinny", x, w, "w", *we, "we");
         CHK(cfg >= 0 && cfg < chronos::kSkinnyW4Configs, "gemm_skinny: W4 cfg");
     } else {
@@ -869,9 +883,10 @@ std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t
         CHK(w.dim() == 2 && w.size(1) == K, "gemm_skinny: w must be [N, K]");
         CHK(cfg >= 0 && cfg < chronos::kSkinnyConfigs, "gemm_skinny: cfg");
     }
-    const int RT = w4 ? chronos::gemm_skinny_w4_rt((int)cfg) : chronos::gemm_skinny_rt((int)cfg);
-    const int MT = w4 ? chronos::gemm_skinny_w4_mt((int)cfg) : chronos::gemm_skinny_mt((int)cfg);
-    const int NW = w4 ? chronos::gemm_skinny_w4_nw((int)cfg) : chronos::gemm_skinny_nw((int)cfg);
+    const int c = (int)cfg;
+    const int RT = w8 ? chronos::gemm_skinny_w8_rt(c) : w4 ? chronos::gemm_skinny_w4_rt(c) : chronos::gemm_skinny_rt(c);
+    const int MT = w8 ? chronos::gemm_skinny_w8_mt(c) : w4 ? chronos::gemm_skinny_w4_mt(c) : chronos::gemm_skinny_mt(c);
+    const int NW = w8 ? chronos::gemm_skinny_w8_nw(c) : w4 ? chronos::gemm_skinny_w4_nw(c) : chronos::gemm_skinny_nw(c);
     CHK(M >= 1 && M <= 16 * MT, "gemm_skinny: M must be in [1, 16 * MT] of the config");
     CHK(splitk >= 1 && K % ((w4 ? 128 : 64) * NW * splitk) == 0 && K <= (1 << 20) && N * K < (1LL << 40),
         w4 ? "gemm_skinny: W4 K % (128 * NW * splitk) == 0" : "gemm_skinny: K % (64 * NW * splitk) == 0");
@@ -880,14 +895,20 @@ std::tuple<Tensor, Tensor> gemm_skinny(const Tensor& x, const Tensor& w, int64_t
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     chronos::PPArgs a{};
     GemmIO io = gemm_io("gemm_skinny", a, x, N, mode, splitk, eps, resid, part_in, 16 * RT);
-    if (w4) {
+    if (w8) {
+        a.w = reinterpret_cast<const uint16_t*>(w.data_ptr<uint8_t>());
+        a.wsc = wscale->data_ptr<float>();
+    } else if (w4) {
         a.w = reinterpret_cast<const uint16_t*>(w.data_ptr<uint8_t>());
         a.wexp = we->data_ptr<uint8_t>();
     } else {
         a.w = bf(w);
     }
     gemm_splitk(a, io, x, mode == 1 ? (N / 2) / (8 * RT) : N / (16 * RT), (int64_t)64 * RT * MT * 4);
-    if (w4) {
+    if (w8) {
+        CHK(chronos::launch_gemm_skinny_w8((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()),
+            "gemm_skinny: W8 launch");
+    } else if (w4) {
         CHK(chronos::launch_gemm_skinny_w4((int)cfg, (int)mode, part_in.has_value(), a, cur_stream()),
             "gemm_skinny: W4 launch");
     } else {
@@ -1107,7 +1128,7 @@ TORCH_LIBRARY(chronos, m) {
     m.def("gemv(Tensor x, Tensor w, bool swiglu, Tensor? ws=None, Tensor? we=None) -> Tensor");
     m.def("gemm(Tensor x, Tensor w, bool swiglu, int stages=3) -> Tensor");
     m.def("gemm_pp(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, bool prio) -> (Tensor, Tensor)");
-    m.def("gemm_skinny(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, Tensor? we=None) "
+    m.def("gemm_skinny(Tensor x, Tensor w, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps, Tensor? we=None, Tensor? wscale=None) "
           "-> (Tensor, Tensor)");
     m.def("gemm_w4m(Tensor x, Tensor q, Tensor e, int mode, int cfg, int splitk, Tensor? resid, Tensor? part_in, float eps) "
           "-> (Tensor, Tensor)");

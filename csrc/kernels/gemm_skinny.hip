@@ -33,6 +33,13 @@
 // On cold 8B weights (scripts/bench_skinny_w4.py, profiles/mxfp4/skinny_table.jsonl; the figures are in the README)
 // it beats the bf16 kernel that the dequantised copy is routed to at M = 2-32 on all four projections, by less at
 // M = 48 / 64 on O and down, and not at QKV and gate_up there, which stay on the copy (ops/gemm_plan.json "w4plans").
+//
+// W8A16 weight mode (WM = kW8, M <= 64: jump-forward chunks and few-stream decode of an fp8 model on bf16 activations):
+// the main loop replaced by w8_stream below — W arrives as e4m3fn bytes [N, K] (PPArgs.w) with per-row f32 scales
+// (PPArgs.wsc), is converted in registers (exact) and feeds the same bf16 MFMA, accumulators, cross-wave reduction,
+// split-K hand-off and epilogues, the row scale applied once to the summed f32 result; own config table (SK8_CONFIGS).
+// The bf16 and W4 instantiations compile to the instructions they had before (profiles/fp8/skinny_isa_same.txt).  It is
+// reached only by ``a16`` callers (ops/gemm.py w8_plan, ops/gemm_plan.json "w8plans"); the measurements are in the README.
 #include <algorithm>
 
 #include "chronos_gemm.h"
@@ -43,7 +50,8 @@ namespace {
 
 enum : int { kPlain = kPPPlain, kSwiglu = kPPSwiglu, kResid = kPPResid };
 // weight mode: bf16 | packed e2m1 + e8m0 block scales (W4A16, OCP MXFP4: PPArgs w = q bytes, wexp = e bytes)
-enum : int { kW16 = 0, kW4 = 2 };
+// | e4m3fn bytes + per-row f32 scales (W8A16: PPArgs w = the bytes, wsc = the scales)
+enum : int { kW16 = 0, kW8 = 1, kW4 = 2 };
 constexpr int XL_MIN_MT = 2;  // x staged through LDS from MT = 2 (x bytes >= the weight bytes per wave)
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -174,11 +182,121 @@ __device__ __forceinline__ void w4_stream(const PPArgs& a, int g, int s, int KS,
         }
     }
 }
+
+// W8A16 main loop (WM = kW8, M <= 64: jump-forward chunks and 3-64 stream decode of an fp8 model on bf16 activations):
+// W streamed as e4m3fn bytes [N, K] (PPArgs.w) with one f32 scale per output row (PPArgs.wsc) — half the bf16 bytes.
+//   * unit = 64 k.  Lane l (r = l & 15, q = l >> 4) loads the 16-B piece of 16 consecutive k of W row r at k0 + 16 q;
+//     its two halves are the A operands of two MFMA steps, each four v_cvt_scalef32_pk_bf16_fp8 with scale 1 (exact:
+//     e4m3 fits bf16, subnormals included; as gemv.hip q2bf): step i covers k0 + 16 q + 8 i .. + 8.  The B operand of
+//     the lane with x row n and the same q is x[n][k0 + 16 q + 8 i .. + 8]: the same k in the same slot, no shuffle;
+//   * a wave's K range is contiguous, as in w4_stream: a unit touches half a 128-B line of each of its 16 rows and the
+//     wave's next unit, in flight with it, the other half.  K % (64 NW splitk) == 0, the bf16 rule: K = 2816 (the
+//     small preset's down projection) is taken by the 4-wave configs;
+//   * x per unit is 16 MT rows x 128 B, the bf16 loop's tile: x bytes / W bytes = 2 MT / RT.  Without XL a lane loads
+//     its two B operands directly (32 contiguous bytes); with XL the tile comes in whole 128-B lines and goes through
+//     the wave's LDS tile exactly like the bf16 loop's, read back at chunk 2 q + i;
+//   * ring stage = RT pieces (4 VGPRs) + 8 MT VGPRs of x: 1 KiB of weights per W tile, half a bf16 stage, so D is twice
+//     the bf16 config's of the same (RT, NW) wherever the registers allow (SK8_CONFIGS below);
+//   * the row scale is not in the loop: the epilogue multiplies the f32 sum by wsc[n] once, after the waves and the
+//     split-K slices are summed and before the NORMP row scale, SwiGLU, the residual add and the store (gemv.hip WQ).
+// hipcc -Rpass-analysis=kernel-resource-usage, per SK8_CONFIGS id (the five epilogue instantiations within 2 VGPRs of
+// each other): no config uses scratch.  VGPRs (+ AGPRs), waves per SIMD:  0: 220 + 16, 2;  1: 190, 2;  2: 160, 3;
+// 3: 96, 5;  4: 118, 4;  5: 220 + 32, 2;  6: 234, 2;  7: 190, 2;  8: 228 + 64, 1;  9: 222, 2;  10: 256 + 46, 1;
+// 11: 120, 4.
+template <int RT, int MT, int D, int NW, int MODE, bool XL>
+__device__ __forceinline__ void w8_stream(const PPArgs& a, int g, int s, int KS, int lane, int wave,
+                                          unsigned char* smem, f32x4 (&acc)[RT][MT]) {
+    const int M = a.M, K = a.K;
+    const int KW = KS / NW;  // this wave's contiguous K range
+    const int NU = KW / 64;  // 64-k units per wave
+    const int kw = s * KS + wave * KW;
+    const int r = lane & 15, q = lane >> 4;
+    const unsigned char* wq = reinterpret_cast<const unsigned char*>(a.w);
+    const i32x4* wp[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        int row;
+        if constexpr (MODE == kSwiglu)
+            row = rt < RT / 2 ? g * 8 * RT + 16 * rt : a.F + g * 8 * RT + 16 * (rt - RT / 2);
+        else
+            row = g * 16 * RT + 16 * rt;
+        wp[rt] = reinterpret_cast<const i32x4*>(wq + (int64_t)(row + r) * K + kw + 16 * q);
+    }
+    // x offsets in 16-B pieces from a.x (M K < 2^31 elements): XL 2 MT line pieces (rows 8 j .. 8 j + 7), else one per tile
+    const bf16x8* xb = reinterpret_cast<const bf16x8*>(a.x);
+    constexpr int NX = XL ? 2 * MT : MT;
+    uint32_t xo[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+        if constexpr (XL)
+            xo[j] = (uint32_t)(((int64_t)min(8 * j + (lane >> 3), M - 1) * K + kw) / 8 + (lane & 7));
+        else
+            xo[j] = (uint32_t)(((int64_t)min(16 * j + r, M - 1) * K + kw) / 8 + 2 * q);
+    }
+    unsigned char* xs = smem + wave * (MT * 2048);  // XL: this wave's x tile, 16 MT rows x 128 B
+
+    i32x4 wr[D][RT];
+    bf16x8 xr[D][MT][2];
+    auto load = [&](int u, int d) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) wr[d][rt] = __builtin_nontemporal_load(wp[rt] + 4 * u);  // 64 k = 64 B
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)  // 64 k = 8 pieces
+                xr[d][mt][i] = XL ? xb[xo[2 * mt + i] + 8 * u] : xb[xo[mt] + 8 * u + i];
+    };
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+        if (d < NU) load(d, d);
+
+    for (int u0 = 0; u0 < NU; u0 += D) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int u = u0 + d;
+            if (u < NU) {
+                if constexpr (XL) {
+                    // line layout -> LDS (row t, chunk lane % 8 in slot chunk ^ (t & 7)) -> MFMA layout (row 16 mt + r,
+                    // chunk 2 q + i); LDS ops of a wave run in order
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const int t = 8 * (2 * mt + h) + (lane >> 3);
+                            *reinterpret_cast<bf16x8*>(xs + t * 128 + (((lane & 7) ^ (t & 7)) << 4)) = xr[d][mt][h];
+                        }
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            const int t = 16 * mt + r;
+                            xr[d][mt][i] = *reinterpret_cast<const bf16x8*>(xs + t * 128 + (((2 * q + i) ^ (t & 7)) << 4));
+                        }
+                }
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int w0 = wr[d][rt][2 * i], w1 = wr[d][rt][2 * i + 1];
+                        const bf16x2 c0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.f, false);
+                        const bf16x2 c1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.f, true);
+                        const bf16x2 c2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.f, false);
+                        const bf16x2 c3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.f, true);
+                        const bf16x8 wa = bf16x8{c0[0], c0[1], c1[0], c1[1], c2[0], c2[1], c3[0], c3[1]};
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+                            acc[rt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xr[d][mt][i], acc[rt][mt], 0, 0, 0);
+                    }
+                if (u + D < NU) load(u + D, d);
+            }
+        }
+    }
+}
 template <int RT, int MT, int D, int NW, int MODE, bool NORMP, int WM = kW16, bool XL4 = false>
 __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     static_assert(MODE != kSwiglu || RT % 2 == 0, "swiglu: RT/2 gate tiles + RT/2 up tiles");
-    constexpr bool W4 = WM == kW4;
-    constexpr bool XL = W4 ? XL4 : MT >= XL_MIN_MT;  // x through the wave's LDS tile (below; W4: per config)
+    constexpr bool W4 = WM == kW4, W8 = WM == kW8;
+    constexpr bool XL = WM != kW16 ? XL4 : MT >= XL_MIN_MT;  // x through the wave's LDS tile (below; W4 / W8: per config)
     constexpr int NT = 64 * NW;                        // threads
     constexpr int UNITS = RT * MT * 64;                // f32x4 accumulators per wave
     constexpr int CPR = MODE == kSwiglu ? 2 * RT : 4 * RT;  // output units (4 columns each) per row
@@ -198,7 +316,8 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     const int task = xcd_remap(blockIdx.x, G * S);
     const int g = task / S, s = task - g * S;
     const int KS = K / S;
-    const int NU = W4 ? 0 : KS / (64 * NW);  // 64-k units per wave (W4: none, this loop is dead and w4_stream runs)
+    // 64-k units per wave (W4 / W8: none, this loop is dead and w4_stream / w8_stream runs)
+    const int NU = WM != kW16 ? 0 : KS / (64 * NW);
     const int kbase = s * KS + wave * 64 + 8 * (lane >> 4);
 
     const bf16x8* wp[RT];
@@ -302,6 +421,7 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
     }
 
     if constexpr (W4) w4_stream<RT, MT, D, NW, MODE, XL>(a, g, s, KS, lane, wave, smem, acc);
+    if constexpr (W8) w8_stream<RT, MT, D, NW, MODE, XL>(a, g, s, KS, lane, wave, smem, acc);
 
     // XL: the reduction slots, inv and the flag alias the other waves' x tiles — wait until every wave's loop is done
     if constexpr (XL) __syncthreads();
@@ -347,6 +467,20 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
 
     f32x4 val[VP][PAIR];
     const bool active = tid < NOUT;  // wave-uniform (NOUT % 64 == 0)
+    // W8: the row scales of this thread's output units, fetched behind the weight ring and in front of the LDS sum
+    f32x4 wv[W8 ? VP : 1][PAIR];
+    if constexpr (W8) {
+        if (active) {
+#pragma unroll
+            for (int j = 0; j < VP; ++j)
+#pragma unroll
+                for (int p = 0; p < PAIR; ++p) {
+                    const int c = (tid + NT * j) % CPR;
+                    const float* sp = a.wsc + (MODE == kSwiglu ? p * a.F + g * 8 * RT : g * 16 * RT) + 4 * c;
+                    wv[j][p] = f32x4{sp[0], sp[1], sp[2], sp[3]};
+                }
+        }
+    }
     if (active) {
 #pragma unroll
         for (int j = 0; j < VP; ++j)
@@ -396,6 +530,12 @@ __global__ void __launch_bounds__(64 * NW) skinny_kernel(PPArgs a) {
         }
     }
     if (!active) return;
+    if constexpr (W8) {
+#pragma unroll
+        for (int j = 0; j < VP; ++j)
+#pragma unroll
+            for (int p = 0; p < PAIR; ++p) val[j][p] *= wv[j][p];
+    }
 
 #pragma unroll
     for (int j = 0; j < VP; ++j) {
@@ -448,7 +588,9 @@ template <int RT, int MT, int D, int NW, int MODE, bool NORMP, int WM = kW16, bo
 void launch_cfg(const PPArgs& a, hipStream_t st) {
     constexpr int UNITS = RT * MT * 64;
     // the reduction slots (+ inv, flag) alias the XL x tiles, which are dead once the main loop ends
-    constexpr int XT = WM == kW4 ? (XL4 ? NW * MT * 4096 : 0) : (MT >= XL_MIN_MT ? NW * MT * 2048 : 0);
+    constexpr int XT = WM == kW4   ? (XL4 ? NW * MT * 4096 : 0)
+                       : WM == kW8 ? (XL4 ? NW * MT * 2048 : 0)
+                                   : (MT >= XL_MIN_MT ? NW * MT * 2048 : 0);
     const int lds = std::max(NW * (UNITS + UNITS / 16) * 16 + 16 * MT * 4 + 16, XT);
     auto kern = skinny_kernel<RT, MT, D, NW, MODE, NORMP, WM, XL4>;
     static bool attr = false;
@@ -526,7 +668,75 @@ bool launch_mode_w4(int cfg, const PPArgs& a, hipStream_t st) {
     }
 }
 
+// W8A16 configs {RT, MT, D (ring depth in 64-k units), NW (K % (64 NW splitk) == 0), XL (x through LDS)}.  A ring
+// stage is 4 RT + 8 MT VGPRs and 1 KiB of weights per W tile — half a bf16 stage — so D is twice the D of the bf16
+// config with the same (RT, NW) where there is one.  The 4-wave configs (0, 5, 8, 10: every MT) take K = 2816.
+#define SK8_CONFIGS(X)    \
+    X(0, 4, 1, 8, 4, 0)   \
+    X(1, 4, 1, 6, 8, 0)   \
+    X(2, 2, 1, 8, 8, 0)   \
+    X(3, 2, 1, 4, 16, 0)  \
+    X(4, 1, 1, 8, 16, 0)  \
+    X(5, 4, 2, 6, 4, 1)   \
+    X(6, 2, 2, 8, 8, 1)   \
+    X(7, 4, 2, 4, 8, 1)   \
+    X(8, 4, 4, 4, 4, 1)   \
+    X(9, 2, 4, 4, 8, 1)   \
+    X(10, 2, 4, 6, 4, 1)  \
+    X(11, 1, 1, 8, 8, 0)
+
+template <int MODE, bool NORMP>
+bool launch_mode_w8(int cfg, const PPArgs& a, hipStream_t st) {
+    switch (cfg) {
+#define SK8_CASE(ID, RT_, MT_, D_, NW_, XL_)                                     \
+    case ID:                                                                     \
+        if constexpr (MODE == kSwiglu && RT_ % 2) return false;                  \
+        else {                                                                   \
+            launch_cfg<RT_, MT_, D_, NW_, MODE, NORMP, kW8, XL_ != 0>(a, st);    \
+            return true;                                                         \
+        }
+        SK8_CONFIGS(SK8_CASE)
+#undef SK8_CASE
+        default: return false;
+    }
+}
+
 }  // namespace
+
+int gemm_skinny_w8_rt(int cfg) {
+    switch (cfg) {
+#define SK8_RT(ID, RT_, MT_, D_, NW_, XL_) case ID: return RT_;
+        SK8_CONFIGS(SK8_RT)
+#undef SK8_RT
+        default: return 0;
+    }
+}
+int gemm_skinny_w8_nw(int cfg) {
+    switch (cfg) {
+#define SK8_NW(ID, RT_, MT_, D_, NW_, XL_) case ID: return NW_;
+        SK8_CONFIGS(SK8_NW)
+#undef SK8_NW
+        default: return 0;
+    }
+}
+int gemm_skinny_w8_mt(int cfg) {
+    switch (cfg) {
+#define SK8_MT(ID, RT_, MT_, D_, NW_, XL_) case ID: return MT_;
+        SK8_CONFIGS(SK8_MT)
+#undef SK8_MT
+        default: return 0;
+    }
+}
+
+// W8A16: a.w = e4m3fn bytes [N, K], a.wsc = f32 row scales [N]; cfg indexes SK8_CONFIGS
+bool launch_gemm_skinny_w8(int cfg, int mode, bool normp, const PPArgs& a, hipStream_t st) {
+    if (a.M == 0) return true;
+    if (a.wsc == nullptr) return false;
+    if (mode == kResid) return normp ? false : launch_mode_w8<kResid, false>(cfg, a, st);
+    if (mode == kSwiglu)
+        return normp ? launch_mode_w8<kSwiglu, true>(cfg, a, st) : launch_mode_w8<kSwiglu, false>(cfg, a, st);
+    return normp ? launch_mode_w8<kPlain, true>(cfg, a, st) : launch_mode_w8<kPlain, false>(cfg, a, st);
+}
 
 int gemm_skinny_w4_rt(int cfg) {
     switch (cfg) {

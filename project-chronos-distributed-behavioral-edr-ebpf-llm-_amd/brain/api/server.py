@@ -263,6 +263,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="projection weights: bf16, fp8 (W8A8 e4m3), mxfp4 (OCP MXFP4 for the low-batch decode GEMV, "
                          "with a resident bf16 copy for every other kernel) or mxfp4-packed (the same numbers without "
                          "the copy: 4.25 bits per weight resident, expanded into one scratch in front of the bf16 GEMMs)")
+    ap.add_argument("--fp8-a16-rows", type=int, default=None,
+                    help="fp8 weights: the largest step (rows, 0-64) that runs on bf16 activations (W8A16); above 2 "
+                         "the skinny MFMA GEMM's fp8-weight mode takes the steps it has a route for (default: "
+                         "CHRONOS_W8A16_ROWS, else 2)")
     ap.add_argument("--max-logprobs", type=int, default=20,
                     help="most top_logprobs a request may ask for (0-20); 0 = logprobs are not offered")
     ap.add_argument("--penalty-window", type=int, default=64,
@@ -288,6 +292,7 @@ def main(argv=None) -> int:
         cfg = EngineConfig(model=a.model, checkpoint=a.checkpoint, tokenizer=a.tokenizer, device=a.device,
                            max_slots=a.max_slots, max_model_len=a.max_model_len, kv_dtype=a.kv_dtype,
                            weight_dtype=a.weights,
+                           **({} if a.fp8_a16_rows is None else {"fp8_a16_rows": a.fp8_a16_rows}),
                            request_timeout_s=a.request_timeout, tp_sequence_parallel=a.sequence_parallel,
                            max_logprobs=a.max_logprobs, penalty_window=a.penalty_window)
         if a.tp > 1 or a.cp > 1:

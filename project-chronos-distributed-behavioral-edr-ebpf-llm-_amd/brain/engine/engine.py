@@ -95,6 +95,11 @@ class EngineConfig:
     # other kernel — a latency mode: bf16 + ~0.27 of it again in memory; "mxfp4-packed": the same numbers without the
     # copy (0.27 of bf16 + one scratch of the largest projection, csrc/kernels/w4_expand.hip), the freed HBM becomes KV
     weight_dtype: str = "bf16"
+    # fp8 weights: the largest step (rows) that runs W8A16 — bf16 activations, no quantisation launches, the bf16 path's
+    # fused epilogues.  Up to 2 rows that is the W8A16 GEMVs (the default, as always); above, up to 64, the skinny MFMA
+    # GEMM's fp8-weight mode, on the steps where all four projections have a route (ops/gemm.py w8_plan); 0 = W8A8
+    # only.  Env CHRONOS_W8A16_ROWS moves the default (the model's own default too), for scripts without the flag
+    fp8_a16_rows: int = field(default_factory=lambda: int(os.environ.get("CHRONOS_W8A16_ROWS", "2")))
     kv_scale: float = 1.0          # fp8 KV scale (stored = value / scale)
     prefill_nqt: int = 8           # 8 = flash prefill kernel (128 query rows / workgroup); 1-2 = split-K kernel
     async_harvest: bool = False    # harvest burst k while burst k+1 runs (hides host work, delays compaction)
@@ -262,6 +267,8 @@ class Engine:
         self.cfg = cfg
         if not 0 <= cfg.penalty_window <= ops.MAX_PENALTY_WINDOW:
             raise ValueError(f"penalty_window must be in 0..{ops.MAX_PENALTY_WINDOW}, not {cfg.penalty_window}")
+        if not 0 <= cfg.fp8_a16_rows <= 64:
+            raise ValueError(f"fp8_a16_rows must be in 0..64, not {cfg.fp8_a16_rows}")
         self.tp = tp or TPContext.single()
         self.cp = cp or TPContext.single()
         if self.cp.world > 1 and self.tp.world > 1:
@@ -283,6 +290,7 @@ class Engine:
         self.load_seconds = time.perf_counter() - t0
         self.model.sequence_parallel = cfg.tp_sequence_parallel and self.tp.world > 1
         self.model.decode_overlap_rows = cfg.tp_decode_overlap if self.tp.world > 1 else 0
+        self.model.w8a16_rows = cfg.fp8_a16_rows
         mc = self.model.cfg
         self.bank = GrammarBank(self.tok.token_bytes_list(), self.tok.stop_ids, mc.vocab_size, cfg.grammar_capacity,
                                 self.device, max_string=cfg.max_string,

@@ -30,8 +30,13 @@ from ..parallel.tp import TPContext
 _FUSE_NORM = os.environ.get("CHRONOS_FUSE_NORM", "1") != "0"
 _FUSE_AR_NORM = os.environ.get("CHRONOS_FUSE_AR_NORM", "1") != "0"
 # fp8-weight decode (T <= 2): W8A16 GEMVs on bf16 activations with the bf16 path's fused norm / RoPE + KV write /
-# residual epilogues instead of W8A8 (an activation-quantisation launch per projection).  Not at T = 3-4: the GEMV's
-# per-row-group overhead makes it slower there than the W8A8 GEMMs (gate_up 140 vs 27 us, profiles/r5/w8a16_*)
+# residual epilogues instead of W8A8 (an activation-quantisation launch per projection).  The GEMV does not carry that
+# further: at T = 3-4 its per-row-group overhead makes it slower than the W8A8 GEMMs (gate_up 140 vs 27 us,
+# profiles/r5/w8a16_*).  Above two rows, up to ``LlamaModel.w8a16_rows`` (default 2 = off, env CHRONOS_W8A16_ROWS, at
+# most 64), a step runs W8A16 on the skinny MFMA GEMM's fp8-weight mode instead (ops/gemm.py ``w8_plan``), and only
+# when every one of a layer's four projections has a route there: a step with one projection unrouted stays wholly
+# W8A8 rather than paying a separate quantisation launch for it.
+_W8A16_ROWS = int(os.environ.get("CHRONOS_W8A16_ROWS", "2"))
 _W8A16_DECODE = os.environ.get("CHRONOS_W8A16_DECODE", "1") != "0"  # TP: fused IPC all-reduce + residual + RMSNorm
 # batched decode (>= 1024 (row, kv head) items, bf16 KV): RoPE + paged-KV write fused into the decode attention
 _FUSE_DECODE_ROPE = os.environ.get("CHRONOS_FUSE_DECODE_ROPE", "1") != "0"
@@ -650,6 +655,9 @@ class LlamaModel:
         # HIP stream, each overlapping the other half's attention / MLP (0 = off)
         self.decode_overlap_rows = 0
         self._comm = None
+        # largest T of an fp8 step that runs W8A16 (set by the engine, EngineConfig.fp8_a16_rows): up to 2 the GEMVs,
+        # above that the skinny GEMM's fp8-weight mode where every projection is routed (``_w8a16_step``)
+        self.w8a16_rows = _W8A16_ROWS
 
     # ---- one micro-batch's pieces of a layer (bf16: x is a tensor; W8A8: x is (e4m3 bytes, row scales)) ----------
     def _norm(self, h, st: dict, w: torch.Tensor, first: bool = False, reduce: bool = False):
@@ -668,16 +676,38 @@ class LlamaModel:
             return ops.quant_rows(h, resid, w, eps, 1 if resid is None else 2)
         return ops.rmsnorm(h, w, eps) if resid is None else ops.add_rmsnorm(h, resid, w, eps)
 
+    def _resid_producer(self, x_cuda: bool, sb: StepBatch, T: int) -> bool:
+        """Whether O / down run as residual producers in this step (shapes permitting)."""
+        return bool(_FUSE_NORM and self.w.norms_folded and self.tp.world == 1 and x_cuda and sb.cp is None
+                    and (sb.tiles is None or T > 2))
+
+    def _w8a16_step(self, T: int, sb: StepBatch, cuda: bool) -> bool:
+        """fp8 weights: does this step run W8A16 (bf16 activations)?  T <= 2: the GEMVs, as always; above, up to
+        ``w8a16_rows``, only when all four projections of a layer have a W8A16 route at T."""
+        cfg, w = self.cfg, self.w
+        if not (w.fp8 and _W8A16_DECODE and cuda and sb.cp is None and sb.dec is None and cfg.hidden_size % 1024 == 0):
+            return False
+        if T > self.w8a16_rows:
+            return False
+        if T <= 2:
+            return True
+        lw = w.layers[0]
+        out = ops.PP_RESID if self._resid_producer(cuda, sb, T) else ops.PP_PLAIN
+        return ops.w8a16_step_ok(T, ((*lw.wqkv.shape, ops.PP_PLAIN), (*lw.wo.shape, out),
+                                     (*lw.w_gu.shape, ops.PP_SWIGLU), (*lw.w_down.shape, out)))
+
     def _out_proj(self, x: torch.Tensor, w: torch.Tensor, st: dict):
         """Row-parallel output projection (o_proj / down_proj).  TP=1: the producer that also adds the residual and
         emits the next RMSNorm's partial sums (ops.ResidOut: the decode GEMV at T <= 2, the batched GEMM's kResid
         epilogue above, prefill included) — the norm then costs no launch: its consumer (QKV / gate_up / LM head)
         applies it as a per-row scale."""
         T = st["T"]
-        if (_FUSE_NORM and self.w.norms_folded and self.tp.world == 1 and x.is_cuda and st["sb"].cp is None
-                and (st["sb"].tiles is None or T > 2) and ops.resid_ok(T, w.shape[0], w.shape[1], ops.is_q(w))):
-            return ops.gemv_resid(x, w, st["resid"])
-        return ops.linear(x, w)
+        a16 = ops.is_q(w) and T > 2  # (an fp8 weight gets here in W8A16 steps only; above two rows: the skinny GEMM)
+        if self._resid_producer(x.is_cuda, st["sb"], T) and (
+                ops.resid_ok_a16(T, w.shape[0], w.shape[1]) if a16
+                else ops.resid_ok(T, w.shape[0], w.shape[1], ops.is_q(w))):
+            return ops.gemv_resid(x, w, st["resid"], a16=a16)
+        return ops.linear(x, w, a16=a16)
 
     def _attn_rows(self, li: int, qkv: torch.Tensor, sb: StepBatch, q_buf: torch.Tensor, kv: KVCache) -> torch.Tensor:
         """RoPE + paged-KV write + attention for the rows of one step batch (prefill tiles or decode rows)."""
@@ -726,7 +756,7 @@ class LlamaModel:
         else:
             # a LazyNorm input goes straight to the projection (the batched GEMM applies the folded norm as a row
             # scale; anything else materialises it)
-            qkv = ops.qlinear(*x, lw.wqkv.q, lw.wqkv.s) if q8 else ops.linear(x, lw.wqkv)
+            qkv = ops.qlinear(*x, lw.wqkv.q, lw.wqkv.s) if q8 else ops.linear(x, lw.wqkv, a16=self.w.fp8 and T > 2)
             if sb.dec is None:
                 attn = self._attn_rows(li, qkv, sb, st["q_buf"], kv)
             else:
@@ -742,7 +772,7 @@ class LlamaModel:
         x = st["x"]
         if self.w.fp8 and not st.get("w16"):
             return ops.qlinear(*ops.qgate_up_quant(*x, lw.w_gu.q, lw.w_gu.s), lw.w_down.q, lw.w_down.s)
-        return self._out_proj(ops.gate_up_silu(x, lw.w_gu), lw.w_down, st)
+        return self._out_proj(ops.gate_up_silu(x, lw.w_gu, a16=self.w.fp8 and st["T"] > 2), lw.w_down, st)
 
     def _forward_sp(self, sb: StepBatch, kv: KVCache, logits_dtype) -> torch.Tensor:
         """TP prefill with sequence parallelism (SURVEY.md §2.5 "Sequence parallel"): every row-parallel output is
@@ -883,8 +913,7 @@ class LlamaModel:
             h = tp.all_reduce(ops.embedding(ids, w.embed, w.vocab_start))
             T = ids.numel()
             st = dict(sb=p, T=T, resid=h, q_buf=torch.empty(T, self.hq, cfg.head_dim, device=h.device, dtype=h.dtype),
-                      w16=(w.fp8 and _W8A16_DECODE and T <= 2 and h.is_cuda and p.cp is None and p.dec is None
-                           and cfg.hidden_size % 1024 == 0))
+                      w16=self._w8a16_step(T, p, h.is_cuda))
             st["x"] = self._norm(h, st, w.layers[0].attn_norm, first=True)
             states.append(st)
         L = len(w.layers)

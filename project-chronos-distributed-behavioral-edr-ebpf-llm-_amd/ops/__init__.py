@@ -16,8 +16,9 @@ import torch
 
 from . import gemm
 from . import reference as ref
-from .gemm import (LazyNorm, ResidOut, W4Scratch, gate_up_silu, gemv_ok, gemv_q_ok, gemv_resid,  # noqa: F401
-                   gemv_w4_ok, is_q, is_w4, linear, resid_ok, w4_dense, w4_expand)
+from .gemm import (PP_PLAIN, PP_RESID, PP_SWIGLU, LazyNorm, ResidOut, W4Scratch, gate_up_silu, gemv_ok,  # noqa: F401
+                   gemv_q_ok, gemv_resid, gemv_w4_ok, is_q, is_w4, linear, resid_ok, resid_ok_a16, w4_dense,
+                   w4_expand, w8a16_step_ok)
 
 _loaded = False
 

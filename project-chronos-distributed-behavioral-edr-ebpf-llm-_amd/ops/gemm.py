@@ -13,7 +13,12 @@ three are one dispatcher, ``_project``, which walks one ladder by weight kind an
   one ``w4_expand`` launch (csrc/kernels/w4_expand.hip) fills in front of the GEMM, the same bits as the copy.  A
   packed-only tensor takes the skinny kernel on every M <= 64 shape it accepts (``w4_plan(packed=True)``);
 * fp8 weights (a QTensor): the W8A16 GEMV at its shapes (M <= 4; the fused norm and the residual producer: M <= 2),
-  else the activations are quantised and the W8A8 op runs (``ops.qlinear``, routed by "qplans");
+  else the activations are quantised and the W8A8 op runs (``ops.qlinear``, routed by "qplans").  Only for a caller
+  that asks with ``a16=True`` (the model in a W8A16 step above two rows, ``LlamaModel.w8a16_rows``), a call the GEMV
+  does not take goes to the W8A16 mode of the skinny kernel (gemm_skinny.hip WM = kW8, M <= 64: e4m3 bytes converted
+  in registers, bf16 activations, the bf16 family's fused norm / SwiGLU / residual epilogues, no quantisation launch)
+  where ``w8_plan`` has a route: a winning row of "w8plans" (``scripts/bench_skinny_w8.py``), or under
+  CHRONOS_W8_SKINNY=model the cost-model pick; without a route it is the W8A8 op as before.  Default calls never ask;
 * bf16 weights, M <= ``GEMV_MAX_M`` (1: single-stream decode): the hand-written GEMV (csrc/kernels/gemv.hip), 1 KiB
   row-contiguous weight streaming — beats hipBLASLt on every decode shape;
 * bf16 weights above: the hand-written MFMA GEMM families with their fused epilogues — the residual epilogue, the
@@ -100,10 +105,20 @@ W4_SKINNY = os.environ.get("CHRONOS_W4_SKINNY", "plan")
 _W4M = {0: (64, 64, 4), 1: (128, 64, 4), 2: (64, 128, 4), 3: (128, 128, 4)}
 W4M_MIN_M, W4M_MAX_M = W4_SKINNY_MAX_M + 1, 512
 W4_MID = os.environ.get("CHRONOS_W4_MID", "plan")
+# W8A16 mode of the same kernel (gemm_skinny.hip SK8_CONFIGS: e4m3 bytes + per-row scales streamed, bf16 MFMA): own
+# config ids -> (RT, MT, NW); the unit is 64 k, so K % (64 NW split-K) == 0 like the bf16 mode, and M <= 64.
+_SK8 = {0: (4, 1, 4), 1: (4, 1, 8), 2: (2, 1, 8), 3: (2, 1, 16), 4: (1, 1, 16), 5: (4, 2, 4), 6: (2, 2, 8),
+        7: (4, 2, 8), 8: (4, 4, 4), 9: (2, 4, 8), 10: (2, 4, 4), 11: (1, 1, 8)}
+W8_SKINNY_MAX_M = 64
+# Which ``a16=True`` QTensor calls the W8A16 GEMV does not take go to that mode (env CHRONOS_W8_SKINNY): ``plan`` = the
+# measured winning rows of gemm_plan.json "w8plans" only, ``off`` = none, ``model`` = the ``_sk8_model`` pick for every
+# valid shape (the tests' way onto the kernel).  Assignable at run time like W4_SKINNY.  Calls without ``a16`` never
+# look at it: what an fp8 weight launches by default is what it launched before the mode existed.
+W8_SKINNY = os.environ.get("CHRONOS_W8_SKINNY", "plan")
 # The measured plans: gemm_plan.json (env CHRONOS_GEMM_PLAN: another file) read once, section -> {(N, K, epilogue):
 # rows sorted by M}.  ``_plan_cache`` holds the answers of the plan functions, keyed by every switch they depend on.
 # ``_plan_table = None`` (or ``_reset_plans()``) makes the next lookup read the file again.
-_PLAN_SECTIONS = ("plans", "qplans", "w4plans", "w4mplans")
+_PLAN_SECTIONS = ("plans", "qplans", "w4plans", "w4mplans", "w8plans")
 _plan_table: Optional[dict] = None
 _plan_cache: dict = {}
 
@@ -129,7 +144,7 @@ def _load_plans() -> dict:
 
 def _reset_plans(**sections) -> None:
     """Forget the plan file and every cached answer; the next lookup reads the file again.  With sections given
-    (``plans=``, ``qplans=``, ``w4plans=``, ``w4mplans=``: tables keyed like the loaded ones) these stand in for the
+    (``plans=``, ``qplans=``, ``w4plans=``, ``w4mplans=``, ``w8plans=``: tables keyed like the loaded ones) these stand in for the
     file, the others empty: the tests' way to inject rows."""
     global _plan_table
     assert set(sections) <= set(_PLAN_SECTIONS), sections
@@ -247,6 +262,53 @@ def w4_plan(m: int, n: int, k: int, mode: int = PP_PLAIN, packed: bool = False) 
         if packed and (out is None or not _sk4_valid(out[0], m, n, k, mode, out[1])):
             out = _sk4_model(m, n, k, mode)
     if out is not None and not _sk4_valid(out[0], m, n, k, mode, out[1]):
+        out = None
+    _plan_cache[key] = out
+    return out
+
+
+def _sk8_valid(c: int, m: int, n: int, k: int, mode: int, sk: int) -> bool:
+    """The binding's rules for the W8A16 skinny mode (bindings.cpp gemm_skinny with ``wscale``)."""
+    if c not in _SK8 or sk < 1 or m < 1 or k < 1 or k > (1 << 20):
+        return False
+    return _skinny_valid(_SK8[c], 64, m, n, k, mode, sk)
+
+
+def _sk8_model(m: int, n: int, k: int, mode: int, cus: int = 256) -> Optional[tuple[int, int]]:
+    """Cost-model pick of a W8A16 skinny config for a shape without a measured row: the narrowest x tile covering M,
+    split-K only while the grid leaves CUs idle, then the widest W tile and the most waves (``_sk4_model``'s order)."""
+    best = None
+    for c, (rt, mt, nw) in _SK8.items():
+        if mt > 1 and m <= 8 * mt:
+            continue
+        groups = (n // 2) // (8 * rt) if mode == PP_SWIGLU else n // (16 * rt)
+        for sk in (1, 2, 4, 7, 8):
+            if not _sk8_valid(c, m, n, k, mode, sk):
+                continue
+            t = (sk > 1 and groups >= cus, -min(groups * sk, cus), sk, -rt, -nw, c)
+            if best is None or t < best[0]:
+                best = (t, (c, sk))
+    return best[1] if best else None
+
+
+def w8_plan(m: int, n: int, k: int, mode: int = PP_PLAIN) -> Optional[tuple[int, int]]:
+    """(W8 config, split-K) of the W8A16 skinny kernel for an ``a16`` QTensor projection at this shape, or None for
+    today's route (W8A8).  ``plan``: gemm_plan.json "w8plans", rows [measured M, cfg, split-K] per (N, K, mode) read
+    like "w4plans" (cfg < 0 = measured and lost; no row = never measured: both None)."""
+    if W8_SKINNY == "off" or m < 1 or m > W8_SKINNY_MAX_M:
+        return None
+    key = ("w8", W8_SKINNY, m, n, k, mode)
+    hit = _plan_cache.get(key, False)
+    if hit is not False:
+        return hit
+    out = None
+    if W8_SKINNY == "model":
+        out = _sk8_model(m, n, k, mode)
+    else:
+        pick = _plan_row("w8plans", (n, k, mode), m)
+        if pick is not None and pick[1] >= 0:
+            out = (int(pick[1]), int(pick[2]))
+    if out is not None and not _sk8_valid(out[0], m, n, k, mode, out[1]):
         out = None
     _plan_cache[key] = out
     return out
@@ -443,6 +505,10 @@ W4_MAX_M = int(os.environ.get("CHRONOS_W4_MAX_M", "1"))
 w4_stats = {"gemv_launches": 0, "skinny_launches": 0, "expand_launches": 0, "mid_launches": 0}
 
 
+# W8A16 skinny GEMM launches issued from Python (captured graphs replay them uncounted)
+w8_stats = {"skinny_launches": 0}
+
+
 def is_w4(w) -> bool:
     """An MXFP4 projection weight (models/llama.py Q4Tensor: packed e2m1 ``q``, e8m0 ``e``, bf16 copy ``w`` — None in
     the packed-only mode)."""
@@ -556,6 +622,20 @@ def _w4_gemm(x, w, mode: int, m: int, n: int, k: int, fuse: bool, resid=None):
     return _k().gemm_skinny(t.reshape(-1, k), w.q, mode, plan[0], plan[1], resid, part, eps, w.e)
 
 
+def _w8_gemm(x, w, mode: int, m: int, n: int, k: int, fuse: bool, resid=None):
+    """The W8A16 skinny launch for an ``a16`` QTensor call the GEMV did not take: (y, partials), or None when
+    ``w8_plan`` has no route (the caller runs the W8A8 op).  ``fuse``: x is a fusable LazyNorm and goes in as the
+    kernel's NORMP prologue."""
+    plan = w8_plan(m, n, k, mode)
+    if plan is None:
+        return None
+    from . import _k
+
+    w8_stats["skinny_launches"] += 1
+    t, resid, part, eps = (x.s, None, x.part, x.eps) if fuse else (LazyNorm.force(x), resid, None, 1e-5)
+    return _k().gemm_skinny(t.reshape(-1, k), w.q, mode, plan[0], plan[1], resid, part, eps, None, w.s)
+
+
 def _q_fallback(x, w, swiglu: bool = False) -> torch.Tensor:
     """fp8 weight off the W8A16 GEMV shapes: quantise the activations and run the W8A8 op."""
     from . import qlinear, quant_rows
@@ -573,11 +653,12 @@ def _gemv_resid(x, w: torch.Tensor, resid: torch.Tensor, ws=None, we=None) -> Re
     return ResidOut(s, _k().gemv_resid(x.reshape(-1, x.shape[-1]), w, resid, s, ws, we))
 
 
-def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> ResidOut:
+def gemv_resid(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, a16: bool = False) -> ResidOut:
     """Producer (O / down projection, TP=1): the new residual stream s = bf16(bf16(x @ w.T) + resid) and the RMSNorm
     partial sums of s^2, in one launch — the GEMV at M <= GEMV_MAX_M, the batched GEMM's kResid epilogue above.  ``w``
-    may be an fp8 QTensor at the W8A16 GEMV shapes (resid_ok(..., fp8=True)).  Only where ``resid_ok`` says so."""
-    return _project(x, w, PP_RESID, resid)
+    may be an fp8 QTensor at the W8A16 GEMV shapes (resid_ok(..., fp8=True)), or with ``a16`` wherever ``resid_ok_a16``
+    says so (the W8A16 skinny kernel's kResid epilogue above the GEMV's rows).  Only where the predicate says so."""
+    return _project(x, w, PP_RESID, resid, a16=a16)
 
 
 def resid_ok(m: int, n: int, k: int, fp8: bool = False) -> bool:
@@ -590,6 +671,26 @@ def resid_ok(m: int, n: int, k: int, fp8: bool = False) -> bool:
     if m <= GEMV_MAX_M:
         return m <= 2 and gemv_ok(m, n, k)  # (the GEMV's residual epilogue: M <= 2)
     return pp_plan(m, n, k, PP_RESID) is not None
+
+
+def resid_ok_a16(m: int, n: int, k: int) -> bool:
+    """The residual-epilogue producer of an fp8 QTensor for an ``a16`` caller: the W8A16 GEMV shapes, as
+    ``resid_ok(..., fp8=True)``, and above two rows the W8A16 skinny kernel's kResid route where ``w8_plan`` has one."""
+    return resid_ok(m, n, k, True) or (m > 2 and w8_plan(m, n, k, PP_RESID) is not None)
+
+
+def w8a16_step_ok(T: int, shapes) -> bool:
+    """True when every projection of a layer has a W8A16 route at T rows — ``shapes``: (N, K, epilogue) of QKV, O,
+    gate_up and down — so that a W8A16 step above the GEMV's rows never pays ``_q_fallback``'s quantisation launch:
+    at T <= 2 the W8A16 GEMV's shapes, above that the skinny kernel's route (``w8_plan``) for each of them."""
+    for n, k, mode in shapes:
+        if T <= 2:
+            ok = resid_ok(T, n, k, True) if mode == PP_RESID else gemv_q_ok(T, n, k)
+        else:
+            ok = w8_plan(T, n, k, mode) is not None
+        if not ok:
+            return False
+    return True
 
 
 def gemv_ok(m: int, n: int, k: int, swiglu: bool = False) -> bool:
@@ -625,11 +726,13 @@ def mfma_gemm(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, stages: in
     return y.view(*x.shape[:-1], y.shape[-1])
 
 
-def _project(x, w, mode: int, resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+def _project(x, w, mode: int, resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+             a16: bool = False):
     """The one dispatcher behind ``linear`` (PP_PLAIN), ``gate_up_silu`` (PP_SWIGLU) and ``gemv_resid`` (PP_RESID, with
     ``resid``): the ladder of the module docstring, walked once.  ``out`` (linear only) keeps the call off every
     Q4Tensor kernel, every fused norm and every planned GEMM: it is the library's ``out=``.  (The plain decode GEMV and
-    the fp8 paths do not look at it and return a new tensor, as they always did.)"""
+    the fp8 paths do not look at it and return a new tensor, as they always did.)  ``a16``: an fp8 QTensor call the
+    W8A16 GEMV does not take may go to the W8A16 skinny kernel (``w8_plan``); it changes nothing for other weights."""
     lazy = isinstance(x, LazyNorm)
     t = x.s if lazy else x
     k = t.shape[-1]
@@ -655,9 +758,16 @@ def _project(x, w, mode: int, resid: Optional[torch.Tensor] = None, out: Optiona
                 return shaped(*hit)
         w = w4_dense(w)
     if is_q(w):  # fp8 weights: the W8A16 GEMV (folded norm fused at M <= 2 when x is a LazyNorm), else W8A8
+        # a16: the GEMV keeps its fused-epilogue rows (M <= 2); above them the skinny kernel where it has a route — at
+        # M = 3-4 too, where the GEMV is the slower of the two (models/llama.py _W8A16_DECODE)
+        gemv = gemv_q_ok(m, n, k)
+        if a16 and t.is_cuda and not (gemv and m <= 2):
+            hit = _w8_gemm(x, w, mode, m, n, k, fuse, resid.reshape(m, -1) if mode == PP_RESID else None)
+            if hit is not None:
+                return shaped(*hit)
         if mode == PP_RESID:
             return _gemv_resid(x, w.q, resid, w.s)
-        if t.is_cuda and gemv_q_ok(m, n, k):
+        if t.is_cuda and gemv:
             return _gemv(x, w.q, swiglu, w.s, None, fuse and m <= 2)
         return _q_fallback(LazyNorm.force(x), w, swiglu)
     if mode == PP_RESID:
@@ -686,11 +796,11 @@ def _project(x, w, mode: int, resid: Optional[torch.Tensor] = None, out: Optiona
     return torch.matmul(x, w.t())
 
 
-def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor) -> torch.Tensor:
+def gate_up_silu(x: torch.Tensor, w_gu: torch.Tensor, a16: bool = False) -> torch.Tensor:
     """silu(x @ gate.T) * (x @ up.T) with w_gu = [gate; up]: one fused launch (GEMV at M <= GEMV_MAX_M, the batched
     GEMM's SwiGLU epilogue above, with the folded input norm when x is a LazyNorm), else GEMM + silu_mul."""
-    return _project(x, w_gu, PP_SWIGLU)
+    return _project(x, w_gu, PP_SWIGLU, a16=a16)
 
 
-def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    return _project(x, w, PP_PLAIN, out=out)
+def linear(x, w: torch.Tensor, out: Optional[torch.Tensor] = None, a16: bool = False) -> torch.Tensor:
+    return _project(x, w, PP_PLAIN, out=out, a16=a16)
