@@ -49,6 +49,12 @@ void launch_apply_penalties(void*, bool, int64_t, int, const int32_t*, int, int,
                             hipStream_t);
 void launch_truncate_logits(void*, bool, int64_t, const int32_t*, int, int, const int16_t*, const int16_t*, int,
                             const int32_t*, const int32_t*, const float*, const float*, const float*, hipStream_t);
+void launch_mirostat_truncate(void*, bool, int64_t, const int32_t*, int, int, const int16_t*, const int16_t*, int,
+                              const int32_t*, const int32_t*, const int32_t*, const float*, const int32_t*, const float*,
+                              float*, float*, int32_t*, hipStream_t);
+void launch_mirostat_update(const void*, bool, int64_t, int, const int32_t*, int, const int32_t*, const int32_t*, int,
+                            const float*, const int32_t*, float*, const float*, const float*, const float*,
+                            const float*, const int32_t*, hipStream_t);
 void launch_gemv(const uint16_t*, int, int, const uint16_t*, int, uint16_t*, bool, hipStream_t);
 void launch_w4_expand(const uint8_t*, const uint8_t*, uint16_t*, int64_t, hipStream_t);
 void attn_init();
@@ -553,6 +559,65 @@ void truncate_logits(const Tensor& logits, const c10::optional<Tensor>& row_of_s
                                     (int)vocab, next.data_ptr<int16_t>(), dist.data_ptr<int16_t>(), (int)done_state,
                                     i32(state), i32(remaining), temperature.data_ptr<float>(),
                                     minp_ln.data_ptr<float>(), typical.data_ptr<float>(), cur_stream());
+}
+
+// Mirostat 2.0 (csrc/kernels/mirostat.hip).  Per slot: mi_on int32 (0 = off), mi_mu / mi_tau / mi_eta f32 (the surprise
+// target and its controller), and the scratch the two kernels hand over: mi_m (legal maximum), mi_lnz (ln Z' of the
+// survivors) f32, mi_mark int32 (the output index the sampler was about to fill, -1 = leave mu alone).
+static void chk_mi(int64_t n, std::initializer_list<const Tensor*> f32s, std::initializer_list<const Tensor*> i32s) {
+    for (const Tensor* t : f32s) {
+        chk_gpu(*t, "mirostat f32 state");
+        CHK(t->scalar_type() == at::kFloat && t->numel() >= n, "mirostat state: f32, one per slot");
+    }
+    for (const Tensor* t : i32s) {
+        chk_i32(*t, "mirostat int32 state");
+        CHK(t->numel() >= n, "mirostat state: int32, one per slot");
+    }
+}
+
+// mirostat_truncate: before the sampler, -inf into the legal tokens of each live sampling slot with mirostat on whose
+// surprise exceeds mu; records m, ln Z' and the mark.
+void mirostat_truncate(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, const Tensor& next,
+                       const Tensor& dist, int64_t done_state, const Tensor& state, const Tensor& remaining,
+                       const Tensor& nout, const Tensor& temperature, const Tensor& mi_on, const Tensor& mi_mu,
+                       const Tensor& mi_m, const Tensor& mi_lnz, const Tensor& mi_mark) {
+    chk_gpu(next, "next");
+    CHK(next.scalar_type() == at::kShort && next.dim() == 2, "next must be int16 [S, V]");
+    chk_gpu(dist, "dist");
+    CHK(dist.scalar_type() == at::kShort && dist.numel() == next.size(0), "dist must be int16 [S]");
+    const int64_t vocab = next.size(1);
+    chk_i32(state, "state");
+    const int64_t n = state.numel();
+    const int32_t* rp = chk_lp_rows(logits, row_of_slot, n);
+    CHK(logits.size(1) >= vocab, "logits narrower than the DFA vocabulary");
+    CHK(vocab < (int64_t(1) << 31) - 1024, "vocabulary too wide");  // the kernel strides 1024 tokens in int
+    chk_mi(n, {&temperature, &mi_mu, &mi_m, &mi_lnz}, {&remaining, &nout, &mi_on, &mi_mark});
+    c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+    chronos::launch_mirostat_truncate(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0), rp, (int)n,
+                                      (int)vocab, next.data_ptr<int16_t>(), dist.data_ptr<int16_t>(), (int)done_state,
+                                      i32(state), i32(remaining), i32(nout), temperature.data_ptr<float>(), i32(mi_on),
+                                      mi_mu.data_ptr<float>(), mi_m.data_ptr<float>(), mi_lnz.data_ptr<float>(),
+                                      i32m(mi_mark), cur_stream());
+}
+
+// mirostat_update: after the sampler, mu <- mu - eta * (S_obs - tau) for the slots whose nout advanced past the mark.
+void mirostat_update(const Tensor& logits, const c10::optional<Tensor>& row_of_slot, const Tensor& nout,
+                     const Tensor& out_tokens, const Tensor& temperature, const Tensor& mi_on, const Tensor& mi_mu,
+                     const Tensor& mi_tau, const Tensor& mi_eta, const Tensor& mi_m, const Tensor& mi_lnz,
+                     const Tensor& mi_mark) {
+    chk_i32(nout, "nout");
+    const int64_t n = nout.numel();
+    const int32_t* rp = chk_lp_rows(logits, row_of_slot, n);
+    CHK(logits.size(1) < (int64_t(1) << 31), "logits too wide");
+    chk_i32(out_tokens, "out_tokens");
+    CHK(out_tokens.dim() == 2 && out_tokens.size(0) >= n, "out_tokens [slots, max_out]");
+    chk_mi(n, {&temperature, &mi_mu, &mi_tau, &mi_eta, &mi_m, &mi_lnz}, {&mi_on, &mi_mark});
+    c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+    chronos::launch_mirostat_update(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0),
+                                    (int)logits.size(1), rp, (int)n, i32(nout), i32(out_tokens),
+                                    (int)out_tokens.size(1), temperature.data_ptr<float>(), i32(mi_on),
+                                    mi_mu.data_ptr<float>(), mi_tau.data_ptr<float>(), mi_eta.data_ptr<float>(),
+                                    mi_m.data_ptr<float>(), mi_lnz.data_ptr<float>(), i32(mi_mark), cur_stream());
 }
 
 // y = x @ w.T for M <= 8 rows (decode); swiglu: w = [gate; up] -> y = silu(x@gate.T) * (x@up.T)
@@ -1174,6 +1239,12 @@ TORCH_LIBRARY(chronos, m) {
           "Tensor out_tokens, Tensor pen_par, Tensor pen_last, Tensor pen_tail, Tensor pen_tlen) -> ()");
     m.def("truncate_logits(Tensor(a!) logits, Tensor? row_of_slot, Tensor next, Tensor dist, int done_state, "
           "Tensor state, Tensor remaining, Tensor temperature, Tensor minp_ln, Tensor typical) -> ()");
+    m.def("mirostat_truncate(Tensor(a!) logits, Tensor? row_of_slot, Tensor next, Tensor dist, int done_state, "
+          "Tensor state, Tensor remaining, Tensor nout, Tensor temperature, Tensor mi_on, Tensor mi_mu, "
+          "Tensor(b!) mi_m, Tensor(c!) mi_lnz, Tensor(d!) mi_mark) -> ()");
+    m.def("mirostat_update(Tensor logits, Tensor? row_of_slot, Tensor nout, Tensor out_tokens, Tensor temperature, "
+          "Tensor mi_on, Tensor(a!) mi_mu, Tensor mi_tau, Tensor mi_eta, Tensor mi_m, Tensor mi_lnz, Tensor mi_mark) "
+          "-> ()");
 }
 
 TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
@@ -1202,6 +1273,8 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("token_logprobs_commit", &token_logprobs_commit);
     m.impl("apply_penalties", &apply_penalties);
     m.impl("truncate_logits", &truncate_logits);
+    m.impl("mirostat_truncate", &mirostat_truncate);
+    m.impl("mirostat_update", &mirostat_update);
     m.impl("ar_all_reduce", &ar_all_reduce);
     m.impl("ar_all_reduce_norm", &ar_all_reduce_norm);
 }

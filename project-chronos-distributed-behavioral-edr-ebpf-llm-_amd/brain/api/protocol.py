@@ -33,8 +33,33 @@ stream=true NDJSON, timing fields in ns) and /api/chat are served too so any Oll
   Ordering deviation from llama.cpp, whose chain is top_k -> typical_p -> top_p -> min_p: here top_k / top_p stay in
   the sampler kernel, so the chain is typical_p -> min_p -> top_k -> top_p, each acting on the survivors of the one
   before.  A backend that cannot apply them (the fake backend) names the non-neutral ones in ``ignored_options``;
-* ``options.mirostat`` (non-zero; ``mirostat_tau`` / ``mirostat_eta`` with it) and ``options.tfs_z`` (other than 1)
-  are not implemented by any backend and are named in ``ignored_options``.
+* ``options.mirostat: 2`` (the integer) is Mirostat 2.0, llama.cpp's ``llama_sampler_mirostat_v2``, with
+  ``options.mirostat_tau`` (target surprise in bits, default 5.0) and ``options.mirostat_eta`` (learning rate,
+  default 0.1), both finite numbers >= 0 (a 400 that names the option otherwise).  It runs on the device inside the
+  decode step (csrc/kernels/mirostat.hip), over the *legal set* (below) and after the request's penalties, when the
+  request samples (temperature T > 0; at temperature 0 the request is greedy, mirostat is neutral and nothing is
+  reported, the same rule as min_p / typical_p).  Per sampled token, with ``m`` the largest legal logit and
+  ``Z = sum exp((logit[u] - m) / T)``: the surprise of ``v`` is ``S(v) = ((m - logit[v]) / T + ln Z) / ln 2`` bits;
+  a token survives iff ``S(v) <= mu`` (if none does, the maxima survive; equal logits share their fate), the others
+  are masked (-inf), the sampler draws from the survivors at temperature T, and with ``t`` the drawn token and ``Z'``
+  the survivors' share of ``Z``: ``mu <- mu - eta * (S_obs - tau)``, ``S_obs = ((m - logit[t]) / T + ln Z') / ln 2``
+  (the surprise under the renormalised distribution, as in llama.cpp).  ``mu`` starts at ``2 * tau`` and is not
+  clamped (llama.cpp has no clamp).  Decisions taken here:
+
+  - *forced tokens leave mu unchanged* (a deviation from llama.cpp, which books surprise 0 for a forced token and
+    so raises ``mu`` by ``eta * tau``): a step with fewer than two legal tokens, or with every legal logit -inf,
+    writes nothing.  Under a schema about half of the tokens are forced and ``mu`` would climb until nothing is
+    truncated.  It also keeps jump-forward consistent: a forced run appended by the host never passes the sampler
+    and does not move ``mu``, so jump-forward stays on for mirostat requests;
+  - *mirostat replaces the truncation chain*: as in llama.cpp the chain is penalties -> temperature -> mirostat,
+    so ``top_k``, ``top_p``, ``min_p`` and ``typical_p`` of such a request are neutral and none of them is
+    reported as ignored: that is the semantics of the option;
+  - *logprobs stay untruncated*: they are taken before the mirostat kernel, like before every other truncation;
+  - a backend that cannot apply it (the fake backend) names ``mirostat`` and whichever of ``mirostat_tau`` /
+    ``mirostat_eta`` were sent in ``ignored_options``;
+* ``options.mirostat`` with any other non-zero value (version 1 needs a sorted top-100 and is not implemented;
+  ``mirostat_tau`` / ``mirostat_eta`` with it) and ``options.tfs_z`` (other than 1; removed from llama.cpp) are
+  not implemented by any backend and are named in ``ignored_options``.
 
 Per-token logprobs (``"logprobs": true`` and optionally ``"top_logprobs": n``, 0 <= n <= 20, both top-level, for
 generate and chat).  The reply gains ``"logprobs": [{"token", "logprob", "bytes", "top_logprobs": [{"token",
@@ -115,6 +140,10 @@ class GenerateParams:
     logprobs: int = -1  # -1 = not asked, 0 = the generated tokens' logprobs, n = with the top n alternatives
     min_p: float = 0.0      # 0 = off
     typical_p: float = 1.0  # 1 = off
+    mirostat: int = 0  # 2 = Mirostat 2.0; any other value the client sent is 0 here and named in ``unsupported``
+    mirostat_tau: float = 5.0
+    mirostat_eta: float = 0.1
+    mirostat_named: tuple = ()  # with mirostat 2: the mirostat options sent, reported when a backend did not apply it
     # options that no backend implements and that are not at their neutral value: always in ``ignored_options``
     unsupported: tuple = ()
 
@@ -185,7 +214,16 @@ class GenerateParams:
         if not 0.0 < p.typical_p <= 1.0:
             raise BadRequest("options.typical_p must be a number above 0 and at most 1")
         un = []
-        if (opts.get("mirostat") or 0) != 0:
+        mi = opts.get("mirostat")
+        if type(mi) is int and mi == 2:
+            p.mirostat = 2
+            for k in ("mirostat_tau", "mirostat_eta"):
+                v = _number(opts, k, getattr(p, k))
+                if v < 0:
+                    raise BadRequest(f"options.{k} must be a finite number of at least 0")
+                setattr(p, k, v)
+            p.mirostat_named = tuple(k for k in ("mirostat", "mirostat_tau", "mirostat_eta") if k in opts)
+        elif (mi or 0) != 0:
             un += [k for k in ("mirostat", "mirostat_tau", "mirostat_eta") if k in opts]
         if opts.get("tfs_z", 1) not in (1, None):
             un.append("tfs_z")
@@ -240,13 +278,21 @@ def penalties_ignored(params: GenerateParams, req) -> tuple:
     """The sampling options of ``params`` to report in ``ignored_options``: its non-neutral penalties when the backend
     did not apply them (a finished engine request carries ``penalty``, a tuple, exactly when its engine did), its
     non-neutral ``min_p`` / ``typical_p`` when the backend has no truncation kernel (a finished engine request carries
-    ``truncates``; at temperature 0 it is False and nothing is reported: greedy has nothing to truncate), and the
-    options no backend implements (``params.unsupported``)."""
+    ``truncates``; at temperature 0 it is False and nothing is reported: greedy has nothing to truncate), the
+    ``mirostat`` options of a ``mirostat: 2`` request when the backend did not apply it (a finished engine request
+    carries ``mirostat``, True exactly when its engine did; a request object without the attribute — the fake backend
+    — never did; an engine request at temperature 0 is greedy and nothing is reported), and the options no backend
+    implements (``params.unsupported``)."""
     pen = () if getattr(req, "penalty", None) else params.ignored
     tr = ()
     if getattr(req, "truncates", None) is None:
         tr = tuple(k for k, neutral in (("min_p", 0.0), ("typical_p", 1.0)) if getattr(params, k) != neutral)
-    return pen + tr + params.unsupported
+    mi = ()
+    if params.mirostat == 2:
+        applied = getattr(req, "mirostat", None)
+        if applied is None or (not applied and params.temperature > 0):
+            mi = params.mirostat_named
+    return pen + tr + mi + params.unsupported
 
 
 def generate_response(model: str, req, ignored: tuple = ()) -> dict:

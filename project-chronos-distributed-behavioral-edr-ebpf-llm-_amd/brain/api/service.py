@@ -128,7 +128,8 @@ class EngineService:
                 meta={"on_tokens": on_tokens} if on_tokens else None, max_len=params.num_ctx or None,
                 logprobs=params.logprobs, repeat_penalty=params.repeat_penalty,
                 frequency_penalty=params.frequency_penalty, presence_penalty=params.presence_penalty,
-                repeat_last_n=params.repeat_last_n, min_p=params.min_p, typical_p=params.typical_p)
+                repeat_last_n=params.repeat_last_n, min_p=params.min_p, typical_p=params.typical_p,
+                mirostat=params.mirostat, mirostat_tau=params.mirostat_tau, mirostat_eta=params.mirostat_eta)
         elif kind == "cancel":
             req = item[1].get("req")
             if req is not None and not req.done_reason:
@@ -322,7 +323,8 @@ class LockstepService(EngineService):
                                             frequency_penalty=params.frequency_penalty,
                                             presence_penalty=params.presence_penalty,
                                             repeat_last_n=params.repeat_last_n, min_p=params.min_p,
-                                            typical_p=params.typical_p)
+                                            typical_p=params.typical_p, mirostat=params.mirostat,
+                                            mirostat_tau=params.mirostat_tau, mirostat_eta=params.mirostat_eta)
         elif kind == "cancel":
             tag = item[1].get("tag")
             if tag is not None:

@@ -194,6 +194,13 @@ class Request:
     # says whether the engine applies them to this request (never at temperature 0: greedy ignores truncation)
     min_p: float = 0.0
     typical_p: float = 1.0
+    # Mirostat 2.0 (csrc/kernels/mirostat.hip).  ``mirostat`` is True only when the engine applies it (options.mirostat
+    # 2 on a request that samples; the API layer looks for this attribute); ``mirostat_mu`` is the surprise target after
+    # the last sampled token (2 * tau before the first), read back at harvest, at preemption and at completion
+    mirostat: bool = False
+    mirostat_tau: float = 5.0
+    mirostat_eta: float = 0.1
+    mirostat_mu: float = 10.0
     # runtime
     pending_text: Optional[tuple] = None  # (prompt, system, raw) until tokenized at admission
     slot: int = -1
@@ -256,6 +263,7 @@ class _Snapshot:
     owners: dict
     seq: int = 0  # order in which snapshots were queued (a jump applied after snapshot k makes k's parked rows stale)
     lp: Optional[tuple] = None  # (logprob ring [n, cols, 1 + K], id ring [n, cols, K]) when an owner wants logprobs
+    mu: Any = None  # mirostat's mu of the first n slots (pinned f32) when an owner runs mirostat
 
 
 class Engine:
@@ -354,6 +362,11 @@ class Engine:
         # min_p / typical_p: ln(min_p) and typical_p per slot, allocated by _tr_alloc when the first request that
         # truncates starts (None = never asked)
         self.s_minpln = self.s_typ = None
+        # mirostat: on flag, mu / tau / eta, and the scratch the two kernels hand over (legal maximum, ln Z' of the
+        # survivors, output-index mark), allocated by _mi_alloc when the first mirostat request starts (None = never
+        # asked); _snap_mu: the harvest snapshots' pinned copies of mu
+        self.s_mion = self.s_mimu = self.s_mitau = self.s_mieta = self.s_mim = self.s_milnz = self.s_mimark = None
+        self._snap_mu: Optional[list] = None
         self.ar = torch.arange(S + 1, **i32)
         self.ar64 = torch.arange(S, dtype=torch.int64, device=dev)
         # ---- scheduling state ----
@@ -365,7 +378,8 @@ class Engine:
         self._rid = itertools.count()
         # (rows, kv splits, steps) -> graph; the variant with the logprob kernels: (rows, kv splits, steps, 1); the
         # variants with the penalty kernel: (rows, kv splits, steps, 0 or 1 for the logprob kernels, "pen"); with the
-        # truncation kernel: (rows, kv splits, steps, 0 or 1 logprobs, 0 or 1 penalties, "tr") — _gkey
+        # truncation kernel: (rows, kv splits, steps, 0 or 1 logprobs, 0 or 1 penalties, "tr"); with the mirostat
+        # kernels: (rows, kv splits, steps, 0 or 1 logprobs, 0 or 1 penalties, 0 or 1 truncation, "mi") — _gkey
         self._graphs: dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
         self.stats = collections.Counter()
@@ -403,7 +417,8 @@ class Engine:
                callback: Callable[[Request], None] | None = None, meta: dict | None = None, top_k: int = 0,
                top_p: float = 1.0, max_len: int | None = None, logprobs: int = -1, repeat_penalty: float = 1.0,
                frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64,
-               min_p: float = 0.0, typical_p: float = 1.0) -> Request:
+               min_p: float = 0.0, typical_p: float = 1.0, mirostat: int = 0, mirostat_tau: float = 5.0,
+               mirostat_eta: float = 0.1) -> Request:
         """Queue a request.  A text prompt is tokenized (chat template) lazily at admission, a prefill chunk's worth
         at a time, so host tokenization of a large wave overlaps the GPU prefill of the previous chunk.
 
@@ -411,7 +426,11 @@ class Engine:
         ``penalty_window`` = clamped to it.  An engine with ``penalty_window`` 0 accepts and does not apply them.
 
         ``min_p`` (0 = off) and ``typical_p`` (1 = off) are llama.cpp's truncation samplers, applied on the device
-        before top-k / top-p (csrc/kernels/truncate.hip); a request at temperature 0 is greedy: they stay neutral."""
+        before top-k / top-p (csrc/kernels/truncate.hip); a request at temperature 0 is greedy: they stay neutral.
+
+        ``mirostat`` 2 is Mirostat 2.0 (csrc/kernels/mirostat.hip) with target surprise ``mirostat_tau`` bits and
+        learning rate ``mirostat_eta``; it replaces the truncation chain (top_k, top_p, min_p and typical_p are set
+        neutral for the request) and is itself neutral at temperature 0.  Any other value is off."""
         n = num_predict if num_predict and num_predict > 0 else self.cfg.default_num_predict
         req = Request(next(self._rid), prompt if isinstance(prompt, list) else [], fmt, min(n, self.cfg.max_out),
                       float(temperature or 0.0), int(seed or 0), callback, meta or {})
@@ -428,6 +447,13 @@ class Engine:
             req.min_p = min(max(float(min_p or 0.0), 0.0), 1.0)
             tp = 1.0 if typical_p is None else float(typical_p)
             req.typical_p = tp if 0.0 < tp < 1.0 else 1.0
+            if mirostat is not None and not isinstance(mirostat, bool) and mirostat == 2:
+                # as in llama.cpp the chain is penalties -> temperature -> mirostat: no other truncation
+                req.mirostat = True
+                req.mirostat_tau = max(float(5.0 if mirostat_tau is None else mirostat_tau), 0.0)
+                req.mirostat_eta = max(float(0.1 if mirostat_eta is None else mirostat_eta), 0.0)
+                req.mirostat_mu = 2.0 * req.mirostat_tau
+                req.top_k, req.top_p, req.min_p, req.typical_p = 0, 1.0, 0.0, 1.0
         if max_len:  # the request's own context window (Ollama options.num_ctx), within the engine's
             req.meta["max_len"] = min(int(max_len), self.cfg.max_model_len)
         req.t_submit = time.perf_counter()
@@ -744,6 +770,8 @@ class Engine:
         lps = []
         if r.logprobs >= 0 and self.s_lp is not None and n:
             lps = self._lp_entries(r, self.s_lp[s, :n].cpu(), self.s_lpids[s, :n].cpu(), n)
+        if r.mirostat and self.s_mimu is not None:  # the re-admitted request resumes from this mu (_init_slots)
+            r.mirostat_mu = float(self.s_mimu[s].item())
         del self.running[s]
         r.slot = -1
         self._free_slots([s])
@@ -927,6 +955,31 @@ class Engine:
             self.s_minpln[sl] = dv(torch.tensor([math.log(r.min_p) if r.min_p > 0 else -math.inf for r in done_reqs],
                                                 dtype=torch.float32))
             self.s_typ[sl] = dv(torch.tensor([r.typical_p for r in done_reqs], dtype=torch.float32))
+        if self.s_mion is None and any(r.mirostat for r in done_reqs):
+            self._mi_alloc()
+        if self.s_mion is not None:  # every starting slot: a reused one may hold a mirostat request's flag and mu
+            f32 = lambda v: dv(torch.tensor(v, dtype=torch.float32))  # noqa: E731
+            self.s_mion[sl] = dv(torch.tensor([int(r.mirostat) for r in done_reqs], dtype=torch.int32))
+            self.s_mimu[sl] = f32([r.mirostat_mu for r in done_reqs])  # 2 * tau, or the mu a preemption saved
+            self.s_mitau[sl] = f32([r.mirostat_tau for r in done_reqs])
+            self.s_mieta[sl] = f32([r.mirostat_eta for r in done_reqs])
+
+    # ---- mirostat ---------------------------------------------------------------------------------------------------
+    def _mi_alloc(self) -> None:
+        S, dev = self.cfg.max_slots, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.s_mion = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.s_mimu, self.s_mitau, self.s_mieta = (torch.zeros(S, **f32) for _ in range(3))
+        self.s_mim, self.s_milnz = torch.zeros(S, **f32), torch.zeros(S, **f32)
+        self.s_mimark = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self._snap_mu = [torch.zeros(S, dtype=torch.float32, pin_memory=dev.type == "cuda") for _ in range(2)]
+
+    def _mi_on(self) -> bool:
+        """Does a mirostat request take part in the sampler launch about to be queued (running, or in ``_starting``)?
+        False at once on an engine that was never asked."""
+        if self.s_mion is None:
+            return False
+        return any(r.mirostat for r in self.running.values()) or any(r.mirostat for r in self._starting)
 
     # ---- min_p / typical_p ------------------------------------------------------------------------------------------
     def _tr_alloc(self) -> None:
@@ -962,9 +1015,12 @@ class Engine:
         return any(r.penalty for r in self.running.values()) or any(r.penalty for r in self._starting)
 
     @staticmethod
-    def _gkey(n: int, ns: int, k: int, lp: bool, pen: bool, tr: bool = False) -> tuple:
+    def _gkey(n: int, ns: int, k: int, lp: bool, pen: bool, tr: bool = False, mi: bool = False) -> tuple:
         """Decode-graph key: (n, ns, k), with the logprob kernels (n, ns, k, 1), with the penalty kernel
-        (n, ns, k, 0 or 1, "pen"), with the truncation kernel (n, ns, k, 0 or 1, 0 or 1, "tr")."""
+        (n, ns, k, 0 or 1, "pen"), with the truncation kernel (n, ns, k, 0 or 1, 0 or 1, "tr"), with the mirostat
+        kernels (n, ns, k, 0 or 1, 0 or 1, 0 or 1, "mi")."""
+        if mi:
+            return (n, ns, k, int(lp), int(pen), int(tr), "mi")
         if tr:
             return (n, ns, k, int(lp), int(pen), "tr")
         if pen:
@@ -1017,7 +1073,9 @@ class Engine:
         them is running or starting in this launch (_lp_on), preceded by the penalty kernel when a penalised one is
         (_pen_on): the logprob kernels and the sampler both see the penalised rows.  The min_p / typical_p kernel
         (_tr_on) runs last before the sampler, after the logprob pre-kernel: logprobs are taken before any truncation,
-        and the commit kernel reads only the chosen token's logit — a survivor's, which truncation never rewrites."""
+        and the commit kernel reads only the chosen token's logit — a survivor's, which truncation never rewrites.
+        The mirostat pair (_mi_on) brackets the sampler innermost: its truncation right before it, its update of mu
+        right after it, before the logprob commit."""
         if self._pen_on():
             ops.apply_penalties(logits, self.s_row, DONE, self.s_state, self.s_nout, self.s_out, self.s_penpar,
                                 self.s_penlast, self.s_pentail, self.s_pentlen)
@@ -1030,9 +1088,18 @@ class Engine:
             ops.truncate_logits(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
                                 self.s_temp, self.s_minpln, self.s_typ)
             self.stats["truncate_launches"] += 1
+        mi = self._mi_on()
+        if mi:
+            ops.mirostat_truncate(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
+                                  self.s_nout, self.s_temp, self.s_mion, self.s_mimu, self.s_mim, self.s_milnz,
+                                  self.s_mimark)
         ops.constrained_sample(logits, self.s_row, self.bank.next, self.bank.dist, DONE, self.s_state, self.s_rem,
                                self.s_temp, self.s_seed, self.s_ids, self.s_pos, self.s_ctx, self.s_nout, self.s_out,
                                self.s_topk, self.s_topp, jump)
+        if mi:
+            ops.mirostat_update(logits, self.s_row, self.s_nout, self.s_out, self.s_temp, self.s_mion, self.s_mimu,
+                                self.s_mitau, self.s_mieta, self.s_mim, self.s_milnz, self.s_mimark)
+            self.stats["mirostat_launches"] += 1
         if lp:
             ops.token_logprobs_commit(logits, self.s_row, self.s_nout, self.s_out, self.s_lpwant, self.s_lpmark,
                                       self.s_lplse, self.s_lptid, self.s_lptval, self.s_lp, self.s_lpids)
@@ -1146,11 +1213,13 @@ class Engine:
     def _decode_rows(self) -> int:
         return _bucket(max(self.running) + 1) if self.running else 0
 
-    def _decode_once(self, n: int, nsplit: int, lp: bool = False, pen: bool = False, tr: bool = False) -> None:
+    def _decode_once(self, n: int, nsplit: int, lp: bool = False, pen: bool = False, tr: bool = False,
+                     mi: bool = False) -> None:
         """One decode step of the first n slots.  ``lp``: a running request wants logprobs, so the sampler launch is
         bracketed by the logprob kernels (and never parks: _jump_flags).  ``pen``: a running request is penalised, so
         the penalty kernel rewrites the logits first.  ``tr``: a running request has a min_p / typical_p, so the
-        truncation kernel runs right before the sampler."""
+        truncation kernel runs right before the sampler.  ``mi``: a running request runs mirostat, so its two kernels
+        bracket the sampler."""
         sb = StepBatch(self.s_ids[:n], self.s_pos[:n], self.ar[:n], self.s_bt[:n], self.ar[:n + 1], self.s_ctx[:n],
                        self.ar64[:n], None, n, 1, nsplit, casc=self._casc)
         logits = self.model.forward(sb, self.kv)
@@ -1164,10 +1233,18 @@ class Engine:
         if tr:
             ops.truncate_logits(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
                                 self.s_temp[:n], self.s_minpln[:n], self.s_typ[:n])
+        if mi:
+            ops.mirostat_truncate(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
+                                  self.s_nout[:n], self.s_temp[:n], self.s_mion[:n], self.s_mimu[:n], self.s_mim[:n],
+                                  self.s_milnz[:n], self.s_mimark[:n])
         ops.constrained_sample(logits, None, self.bank.next, self.bank.dist, DONE, self.s_state[:n], self.s_rem[:n],
                                self.s_temp[:n], self.s_seed[:n], self.s_ids[:n], self.s_pos[:n], self.s_ctx[:n],
                                self.s_nout[:n], self.s_out[:n], self.s_topk[:n], self.s_topp[:n],
                                None if lp else self._jump_flags(n))
+        if mi:
+            ops.mirostat_update(logits, None, self.s_nout[:n], self.s_out[:n], self.s_temp[:n], self.s_mion[:n],
+                                self.s_mimu[:n], self.s_mitau[:n], self.s_mieta[:n], self.s_mim[:n], self.s_milnz[:n],
+                                self.s_mimark[:n])
         if lp:
             ops.token_logprobs_commit(logits, None, self.s_nout[:n], self.s_out[:n], self.s_lpwant[:n],
                                       self.s_lpmark[:n], self.s_lplse[:n], self.s_lptid[:n], self.s_lptval[:n],
@@ -1219,19 +1296,21 @@ class Engine:
         self._update_casc()
         n = min(self._decode_rows(), self.cfg.max_slots)
         ns = self._nsplit(n, self._ctx_class())
-        lp, pen, tr = self._lp_on(), self._pen_on(), self._tr_on()
+        lp, pen, tr, mi = self._lp_on(), self._pen_on(), self._tr_on(), self._mi_on()
         if self.device.type == "cuda" and self.cfg.use_graphs:
-            g = self._graphs.get(self._gkey(n, ns, k, lp, pen, tr))
+            g = self._graphs.get(self._gkey(n, ns, k, lp, pen, tr, mi))
             if g is None:
-                g = self._capture(n, ns, k, lp, pen, tr)
+                g = self._capture(n, ns, k, lp, pen, tr, mi)
             g.replay()
         else:
             self._gate(n)
             try:
                 for _ in range(k):
-                    self._decode_once(n, ns, lp, pen, tr)
+                    self._decode_once(n, ns, lp, pen, tr, mi)
             finally:
                 self._gate(0)
+        if mi:
+            self.stats["mirostat_launches"] += k
         if tr:
             self.stats["truncate_launches"] += k
         if lp:
@@ -1264,11 +1343,15 @@ class Engine:
                 lp = (fl[:n * cols * (1 + K)].view(n, cols, 1 + K), fi[:n * cols * K].view(n, cols, K))
                 lp[0].copy_(self.s_lp[:n, :cols], non_blocking=True)
                 lp[1].copy_(self.s_lpids[:n, :cols], non_blocking=True)
+        mu = None
+        if self.s_mimu is not None and any(r.mirostat for r in self.running.values()):
+            mu = self._snap_mu[self._snap_i ^ 1][:n]
+            mu.copy_(self.s_mimu[:n], non_blocking=True)
         ev = None
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
             ev.record()
-        return _Snapshot(n, ev, st, no, out, dict(self.running), self._snap_seq, lp)
+        return _Snapshot(n, ev, st, no, out, dict(self.running), self._snap_seq, lp, mu)
 
     def _gate(self, n: int) -> None:
         """Arm the decode early-exit gate for a small bucket (n <= 8 rows): the steps of a burst after every row's
@@ -1276,8 +1359,8 @@ class Engine:
         if self.device.type == "cuda" and self.cfg.decode_gate:
             ops.set_decode_gate(self.s_state, n if 0 < n <= 8 else 0)
 
-    def _capture(self, n: int, ns: int, k: int, lp: bool = False, pen: bool = False,
-                 tr: bool = False) -> "torch.cuda.CUDAGraph":
+    def _capture(self, n: int, ns: int, k: int, lp: bool = False, pen: bool = False, tr: bool = False,
+                 mi: bool = False) -> "torch.cuda.CUDAGraph":
         if self._graph_pool is None:
             self._graph_pool = torch.cuda.graph_pool_handle()
         g = torch.cuda.CUDAGraph()
@@ -1286,10 +1369,10 @@ class Engine:
         try:
             with torch.cuda.graph(g, pool=self._graph_pool):
                 for _ in range(k):
-                    self._decode_once(n, ns, lp, pen, tr)
+                    self._decode_once(n, ns, lp, pen, tr, mi)
         finally:
             self._gate(0)
-        self._graphs[self._gkey(n, ns, k, lp, pen, tr)] = g
+        self._graphs[self._gkey(n, ns, k, lp, pen, tr, mi)] = g
         self.stats["graphs_captured"] += 1
         return g
 
@@ -1326,6 +1409,11 @@ class Engine:
         parked = [(s, r) for s in np.flatnonzero(st <= -2).tolist()
                   if (r := alive(s)) is not None and r.meta.get("jump_seq", 0) < seq]
         streaming = [(s, r) for s, r in owners.items() if r.meta.get("on_tokens") and alive(s) is not None]
+        if snap.mu is not None:  # mirostat's mu as of this snapshot (a jump applied below does not move it)
+            mus = snap.mu.numpy()
+            for s, r in owners.items():
+                if r.mirostat and s < snap.n and alive(s) is not None:
+                    r.mirostat_mu = float(mus[s])
         ended = {}  # slot -> output ids of jumped runs that end the verdict
         if parked:
             t = time.perf_counter()
@@ -1489,6 +1577,8 @@ class Engine:
                 lp += (self.s_pentail, self.s_pentlen)
         if self.s_minpln is not None:  # and the min_p / typical_p parameters
             lp += (self.s_minpln, self.s_typ)
+        if self.s_mion is not None:  # and mirostat's flag, mu and controller (its scratch lives within one launch)
+            lp += (self.s_mion, self.s_mimu, self.s_mitau, self.s_mieta)
         for t in (self.s_ids, self.s_pos, self.s_ctx, self.s_state, self.s_rem, self.s_nout, self.s_seed, self.s_temp,
                   self.s_topk, self.s_topp, self.s_out, self.s_bt, *lp):
             t[di] = t[si]

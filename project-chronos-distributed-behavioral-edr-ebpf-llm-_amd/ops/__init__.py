@@ -4,8 +4,8 @@ There is no silent fallback on a GPU: a CUDA/HIP tensor always goes to ``torch.o
 extension (``_C*.so``, built by :mod:`chronos.native`) cannot be built or loaded the op raises.  CPU tensors (tests,
 the gloo-backed distributed tests, the CPU plumbing config) take :mod:`.reference`.
 
-Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties,truncate,w4_expand}.hip (SURVEY.md §2.3
-K1-K14).
+Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties,truncate,mirostat,
+w4_expand}.hip.
 """
 from __future__ import annotations
 
@@ -426,6 +426,70 @@ def truncate_survivors(x, legal, minp_ln: float, typical: float, dtype=torch.flo
     """The reference survivor mask of one row (:func:`.reference.truncate_survivors`): what ``truncate_logits`` keeps
     of the ``legal`` tokens of logits row ``x``."""
     return ref.truncate_survivors(x, legal, minp_ln, typical, dtype)
+
+
+def _check_mirostat(what: str, logits, row_of_slot, n: int, per_slot: tuple, mi_mark, max_out=None):
+    if row_of_slot is not None:
+        rs = row_of_slot.cpu().long()
+        _need(row_of_slot.shape[0] >= n, f"{what}: row_of_slot shorter than the slots")
+        _need(bool(((rs >= -1) & (rs < logits.shape[0])).all()), f"{what}: logits row out of range")
+    else:
+        _need(n <= logits.shape[0], f"{what}: more slots than logits rows")
+    _need(min(t.shape[0] for t in per_slot) >= n, f"{what}: per-slot shapes")
+    if max_out is not None:
+        mk = mi_mark[:n].cpu().long()
+        _need(bool(((mk >= -1) & (mk <= max_out)).all()), f"{what}: mi_mark out of range")
+
+
+def mirostat_truncate(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, nout, temperature, mi_on,
+                      mi_mu, mi_m, mi_lnz, mi_mark) -> None:
+    """Launched AFTER ``apply_penalties`` / ``token_logprobs`` and BEFORE ``constrained_sample`` on the same logits:
+    Mirostat 2.0's truncation, in place.  For every live slot (the sampler's test, row addressing and legal set) with
+    ``mi_on`` set and ``temperature`` T > 0, the legal tokens whose surprise ``((m - x) / T + ln Z) / ln 2`` exceeds
+    ``mi_mu[slot]`` get -inf in the row's dtype (the maxima always survive), and the slot records ``mi_m`` = m,
+    ``mi_lnz`` = ln Z' of the survivors and ``mi_mark = nout``.  A forced step (fewer than two legal tokens, or every
+    legal logit -inf) and every slot that is skipped, greedy or off get ``mi_mark = -1`` and no logit is touched
+    (csrc/kernels/mirostat.hip)."""
+    if _checking(logits):
+        st = state.cpu().long()
+        S, n = next_tab.shape[0], state.shape[0]
+        _need(bool(((st >= -1 - S) & (st < S)).all()), "mirostat_truncate: grammar state out of range")
+        _need(next_tab.shape[1] <= logits.shape[-1], "mirostat_truncate: grammar table wider than the logits")
+        _need(dist.shape[0] == S, "mirostat_truncate: dist must have one entry per grammar state")
+        _check_mirostat("mirostat_truncate", logits, row_of_slot, n,
+                        (remaining, nout, temperature, mi_on, mi_mu, mi_m, mi_lnz, mi_mark), mi_mark)
+        _need(bool((nout[:n].cpu().long() >= 0).all()), "mirostat_truncate: negative output count")
+    if logits.is_cuda:
+        _k().mirostat_truncate(logits, row_of_slot, next_tab, dist, done_state, state, remaining, nout, temperature,
+                               mi_on, mi_mu, mi_m, mi_lnz, mi_mark)
+    else:
+        ref.mirostat_truncate(logits, row_of_slot, next_tab, dist, done_state, state, remaining, nout, temperature,
+                              mi_on, mi_mu, mi_m, mi_lnz, mi_mark)
+
+
+def mirostat_update(logits, row_of_slot, nout, out_tokens, temperature, mi_on, mi_mu, mi_tau, mi_eta, mi_m, mi_lnz,
+                    mi_mark) -> None:
+    """Launched AFTER ``constrained_sample``: where the sampler emitted output index ``i = mi_mark[slot]`` (``nout ==
+    i + 1``, ``i < max_out``) with token ``t``, ``mi_mu -= mi_eta * (S_obs - mi_tau)`` with ``S_obs = ((mi_m -
+    logit[t]) / T + mi_lnz) / ln 2``, the surprise of ``t`` among the survivors.  Nothing else is written."""
+    if _checking(logits):
+        n = nout.shape[0]
+        _need(out_tokens.shape[0] >= n, "mirostat_update: out_tokens shorter than the slots")
+        _check_mirostat("mirostat_update", logits, row_of_slot, n,
+                        (temperature, mi_on, mi_mu, mi_tau, mi_eta, mi_m, mi_lnz, mi_mark), mi_mark,
+                        out_tokens.shape[1])
+    if logits.is_cuda:
+        _k().mirostat_update(logits, row_of_slot, nout, out_tokens, temperature, mi_on, mi_mu, mi_tau, mi_eta, mi_m,
+                             mi_lnz, mi_mark)
+    else:
+        ref.mirostat_update(logits, row_of_slot, nout, out_tokens, temperature, mi_on, mi_mu, mi_tau, mi_eta, mi_m,
+                            mi_lnz, mi_mark)
+
+
+def mirostat_row(x, legal, temperature: float, mu: float, dtype=torch.float32):
+    """The reference survivors of one row (:func:`.reference.mirostat_row`): ``(keep, m, ln Z')`` or ``None`` for a
+    forced step."""
+    return ref.mirostat_row(x, legal, temperature, mu, dtype)
 
 
 def attention_tiles(q_lens: list[int], hq: int, hkv: int, nqt: int) -> list[tuple[int, int]]:

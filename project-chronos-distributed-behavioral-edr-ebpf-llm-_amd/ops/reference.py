@@ -445,3 +445,76 @@ def truncate_logits(logits, row_of_slot, next_tab, dist, done_state: int, state,
         kill = (legal & ~keep).nonzero().flatten()
         if kill.numel():
             logits[row, kill] = float("-inf")
+
+
+_INV_LN2 = 1.4426950408889634
+
+
+def mirostat_row(x: torch.Tensor, legal: torch.Tensor, temperature: float, mu: float, dtype=torch.float32):
+    """One row of Mirostat 2.0's truncation (csrc/kernels/mirostat.hip, steps 1 to 3): over the ``legal`` tokens of
+    logits row ``x`` [V], with ``m = max x`` and ``Z = sum exp((x - m) / T)``, the surprise in bits is
+    ``S = ((m - x) / T + ln Z) / ln 2``; a token survives iff ``S <= mu`` or ``x == m``.  Returns ``(keep, m, lnz)``:
+    the bool [V] survivor mask (a subset of ``legal``), the maximum and ``ln Z'`` of the survivors as 0-d tensors of
+    ``dtype`` — or ``None`` for a forced step (fewer than two legal tokens, or no legal logit above -inf).  ``dtype``:
+    the arithmetic's precision (float64 gives the tests their yardstick)."""
+    idx = legal.nonzero().flatten()
+    if idx.numel() < 2:
+        return None
+    xl = x.float()[idx].to(dtype)
+    m = xl.max()
+    if float(m) == float("-inf"):
+        return None
+    T = torch.tensor(temperature, dtype=torch.float32).to(dtype)
+    e = torch.exp((xl - m) / T)
+    s = ((m - xl) / T + torch.log(e.sum())) * torch.tensor(_INV_LN2, dtype=dtype)
+    alive = (xl == m) | (s <= torch.tensor(mu, dtype=torch.float32).to(dtype))
+    keep = torch.zeros_like(legal)
+    keep[idx] = alive
+    return keep, m, torch.log(e[alive].sum())
+
+
+def mirostat_truncate(logits, row_of_slot, next_tab, dist, done_state: int, state, remaining, nout, temperature, mi_on,
+                      mi_mu, mi_m, mi_lnz, mi_mark) -> None:
+    """fp32 reference of mirostat_truncate_kernel (host loop over the slots): -inf, in place, into the legal tokens of
+    each live sampling slot with mirostat on whose surprise exceeds the slot's mu; ``mi_m`` / ``mi_lnz`` / ``mi_mark =
+    nout`` for the update.  Every slot it does not truncate — skipped, greedy, off, forced — gets ``mi_mark = -1``."""
+    V = next_tab.shape[1]
+    for slot in range(state.numel()):
+        mi_mark[slot] = -1
+        s = int(state[slot])
+        row = int(row_of_slot[slot]) if row_of_slot is not None else slot
+        T = float(temperature[slot])
+        if not int(mi_on[slot]) or s < 0 or s == done_state or row < 0 or not T > 0.0:
+            continue
+        nx = next_tab[s].long()
+        legal = (nx >= 0) & (dist[nx.clamp(min=0)].long() <= int(remaining[slot]) - 1)
+        res = mirostat_row(logits[row, :V], legal, T, float(mi_mu[slot]))
+        if res is None:
+            continue
+        keep, m, lnz = res
+        kill = (legal & ~keep & (logits[row, :V].float() > float("-inf"))).nonzero().flatten()
+        if kill.numel():
+            logits[row, kill] = float("-inf")
+        mi_m[slot] = m
+        mi_lnz[slot] = lnz
+        mi_mark[slot] = int(nout[slot])
+
+
+def mirostat_update(logits, row_of_slot, nout, out_tokens, temperature, mi_on, mi_mu, mi_tau, mi_eta, mi_m, mi_lnz,
+                    mi_mark) -> None:
+    """fp32 reference of mirostat_update_kernel: where the sampler emitted output index ``i = mi_mark[slot]`` (``nout
+    == i + 1``) with token ``t``, ``S_obs = ((m - x_t) / T + ln Z') / ln 2`` and ``mu <- mu - eta * (S_obs - tau)``."""
+    max_out = out_tokens.shape[1]
+    for slot in range(nout.numel()):
+        i = int(mi_mark[slot])
+        if i < 0 or i >= max_out or not int(mi_on[slot]) or int(nout[slot]) != i + 1:
+            continue
+        row = int(row_of_slot[slot]) if row_of_slot is not None else slot
+        T = temperature[slot].float()
+        tok = int(out_tokens[slot, i])
+        if row < 0 or not float(T) > 0.0 or not 0 <= tok < logits.shape[1]:
+            continue
+        sobs = ((mi_m[slot] - logits[row, tok].float()) / T + mi_lnz[slot]) * torch.tensor(_INV_LN2)
+        if not bool(torch.isfinite(sobs)):
+            continue
+        mi_mu[slot] = mi_mu[slot] - mi_eta[slot] * (sobs - mi_tau[slot])

@@ -60,7 +60,8 @@ def _worker(rank: int, cfg_dict: dict, req_q, res_q, device: str, fail_start: bo
                                          out_ids=list(r.out_ids), done_reason=r.done_reason, t_submit=r.t_submit,
                                          t_admit=r.t_admit, t_first=r.t_first, t_done=r.t_done, rank=rank,
                                          logprobs=r.logprobs, out_logprobs=list(r.out_logprobs),
-                                         penalty=r.penalty, truncates=r.truncates)))
+                                         penalty=r.penalty, truncates=r.truncates,
+                                         mirostat=r.mirostat, mirostat_mu=r.mirostat_mu)))
         return cb
 
     def tokens(rid):
@@ -94,7 +95,8 @@ def _worker(rank: int, cfg_dict: dict, req_q, res_q, device: str, fail_start: bo
                                    meta={"rid": rid, **({"on_tokens": tokens(rid)} if stream else {})},
                                    max_len=p.num_ctx or None, logprobs=p.logprobs, repeat_penalty=p.repeat_penalty,
                                    frequency_penalty=p.frequency_penalty, presence_penalty=p.presence_penalty,
-                                   repeat_last_n=p.repeat_last_n, min_p=p.min_p, typical_p=p.typical_p)
+                                   repeat_last_n=p.repeat_last_n, min_p=p.min_p, typical_p=p.typical_p,
+                                   mirostat=p.mirostat, mirostat_tau=p.mirostat_tau, mirostat_eta=p.mirostat_eta)
             try:
                 item = req_q.get_nowait()
             except queue.Empty:

@@ -42,6 +42,7 @@ class _Sub:
     logprobs: int = -1  # every rank holds the all-gathered logits, so the ranks' logprobs agree with no extra traffic
     penalties: tuple = (1.0, 0.0, 0.0, 64)  # (repeat, frequency, presence, repeat_last_n): applied by every rank alike
     truncation: tuple = (0.0, 1.0)  # (min_p, typical_p): likewise
+    mirostat: tuple = (0, 5.0, 0.1)  # (mirostat, tau, eta): likewise; every rank keeps its own, identical, mu
 
 
 @dataclass
@@ -79,7 +80,8 @@ class TPEngine:
                callback: Callable[[Request], None] | None = None, top_k: int = 0, top_p: float = 1.0,
                max_len: int | None = None, logprobs: int = -1, repeat_penalty: float = 1.0,
                frequency_penalty: float = 0.0, presence_penalty: float = 0.0, repeat_last_n: int = 64,
-               min_p: float = 0.0, typical_p: float = 1.0) -> int:
+               min_p: float = 0.0, typical_p: float = 1.0, mirostat: int = 0, mirostat_tau: float = 5.0,
+               mirostat_eta: float = 0.1) -> int:
         assert self.leader, "requests enter through TP rank 0"
         ids = prompt if isinstance(prompt, list) else self.engine.tok.chat_ids(prompt)
         with self._lock:
@@ -89,7 +91,7 @@ class TPEngine:
                 self._callbacks[tag] = callback
         self._inbox.put(_Sub(ids, fmt, num_predict, temperature, seed, tag, top_k, top_p, max_len, logprobs,
                              (repeat_penalty, frequency_penalty, presence_penalty, repeat_last_n),
-                             (min_p, typical_p)))
+                             (min_p, typical_p), (mirostat, mirostat_tau, mirostat_eta)))
         return tag
 
     def cancel(self, tag: int, reason: str = "cancelled") -> None:
@@ -146,7 +148,8 @@ class TPEngine:
                                    max_len=s.max_len, logprobs=s.logprobs, repeat_penalty=s.penalties[0],
                                    frequency_penalty=s.penalties[1], presence_penalty=s.penalties[2],
                                    repeat_last_n=s.penalties[3], min_p=s.truncation[0],
-                                   typical_p=s.truncation[1])
+                                   typical_p=s.truncation[1], mirostat=s.mirostat[0], mirostat_tau=s.mirostat[1],
+                                   mirostat_eta=s.mirostat[2])
             if not r.done_reason:
                 self._reqs[s.tag] = r
         for tag, reason in msg.cancels:
