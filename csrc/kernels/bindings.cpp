@@ -55,6 +55,11 @@ void launch_mirostat_truncate(void*, bool, int64_t, const int32_t*, int, int, co
 void launch_mirostat_update(const void*, bool, int64_t, int, const int32_t*, int, const int32_t*, const int32_t*, int,
                             const float*, const int32_t*, float*, const float*, const float*, const float*,
                             const float*, const int32_t*, hipStream_t);
+int pool_max_items(int, int);
+int pool_max_seqs();
+void launch_pool_accum(const uint16_t*, int, int, float, const int32_t*, const int32_t*, int, float*, int, int32_t*,
+                       float*, hipStream_t);
+void launch_pool_finish(float*, int, int, const int32_t*, int, const uint16_t*, float*, hipStream_t);
 void launch_gemv(const uint16_t*, int, int, const uint16_t*, int, uint16_t*, bool, hipStream_t);
 void launch_w4_expand(const uint8_t*, const uint8_t*, uint16_t*, int64_t, hipStream_t);
 void attn_init();
@@ -618,6 +623,52 @@ void mirostat_update(const Tensor& logits, const c10::optional<Tensor>& row_of_s
                                     (int)out_tokens.size(1), temperature.data_ptr<float>(), i32(mi_on),
                                     mi_mu.data_ptr<float>(), mi_tau.data_ptr<float>(), mi_eta.data_ptr<float>(),
                                     mi_m.data_ptr<float>(), mi_lnz.data_ptr<float>(), i32(mi_mark), cur_stream());
+}
+
+// Embedding pooling (csrc/kernels/pool.hip).  H is one of the presets' hidden sizes: the kernels are compiled per H.
+static void chk_pool_acc(const Tensor& acc, int64_t H) {
+    chk_gpu(acc, "acc");
+    CHK(acc.scalar_type() == at::kFloat && acc.dim() == 2 && acc.size(1) == H, "pool: acc must be f32 [S, H]");
+    CHK(H == 256 || H == 1024 || H == 4096 || H == 8192, "pool: hidden size must be 256, 1024, 4096 or 8192");
+    CHK(acc.size(0) < (int64_t(1) << 31) / H, "pool: acc too large");
+}
+
+// pool_accum: acc[sel[b]] += sum over rows [q_rows[b][0], q_rows[b][1]) of s[r] * rsqrt(mean(s[r]^2) + eps), fp32.
+void pool_accum(const Tensor& s, double eps, const Tensor& q_rows, const Tensor& sel, const Tensor& acc) {
+    chk_bf16(s, "s");
+    CHK(s.dim() == 2, "pool_accum: s must be [T, H]");
+    const int64_t T = s.size(0), H = s.size(1);
+    chk_pool_acc(acc, H);
+    chk_i32(q_rows, "q_rows");
+    chk_i32(sel, "sel");
+    const int64_t B = sel.numel();
+    CHK(q_rows.dim() == 2 && q_rows.size(0) == B && q_rows.size(1) == 2, "pool_accum: q_rows must be [B, 2]");
+    CHK(B <= chronos::pool_max_seqs(), "pool_accum: too many sequences in one call");
+    CHK(T < (int64_t(1) << 30), "pool_accum: too many rows");
+    if (B == 0 || T == 0) return;
+    c10::hip::HIPGuardMasqueradingAsCUDA g(s.device());
+    const int64_t items = chronos::pool_max_items((int)T, (int)B);
+    auto plan = at::empty({2 + B + 1 + items}, sel.options());
+    auto scratch = at::empty({items, H}, acc.options());
+    chronos::launch_pool_accum(bf(s), (int)T, (int)H, (float)eps, i32(q_rows), i32(sel), (int)B,
+                               acc.data_ptr<float>(), (int)acc.size(0), i32m(plan), scratch.data_ptr<float>(),
+                               cur_stream());
+}
+
+// pool_finish: out[i] = normalise(g (.) acc[rows[i]]) (zeros at norm 0), then acc[rows[i]] <- 0.
+void pool_finish(const Tensor& acc, const Tensor& rows, const Tensor& g, const Tensor& out) {
+    chk_bf16(g, "g");
+    const int64_t H = g.numel();
+    chk_pool_acc(acc, H);
+    chk_i32(rows, "rows");
+    chk_gpu(out, "out");
+    const int64_t n = rows.numel();
+    CHK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == n && out.size(1) == H,
+        "pool_finish: out must be f32 [n, H]");
+    CHK(n < (int64_t(1) << 31) / H, "pool_finish: too many rows");
+    c10::hip::HIPGuardMasqueradingAsCUDA gd(acc.device());
+    chronos::launch_pool_finish(acc.data_ptr<float>(), (int)acc.size(0), (int)H, i32(rows), (int)n, bf(g),
+                                out.data_ptr<float>(), cur_stream());
 }
 
 // y = x @ w.T for M <= 8 rows (decode); swiglu: w = [gate; up] -> y = silu(x@gate.T) * (x@up.T)
@@ -1245,6 +1296,8 @@ TORCH_LIBRARY(chronos, m) {
     m.def("mirostat_update(Tensor logits, Tensor? row_of_slot, Tensor nout, Tensor out_tokens, Tensor temperature, "
           "Tensor mi_on, Tensor(a!) mi_mu, Tensor mi_tau, Tensor mi_eta, Tensor mi_m, Tensor mi_lnz, Tensor mi_mark) "
           "-> ()");
+    m.def("pool_accum(Tensor s, float eps, Tensor q_rows, Tensor sel, Tensor(a!) acc) -> ()");
+    m.def("pool_finish(Tensor(a!) acc, Tensor rows, Tensor g, Tensor(b!) out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
@@ -1275,6 +1328,8 @@ TORCH_LIBRARY_IMPL(chronos, CUDA, m) {
     m.impl("truncate_logits", &truncate_logits);
     m.impl("mirostat_truncate", &mirostat_truncate);
     m.impl("mirostat_update", &mirostat_update);
+    m.impl("pool_accum", &pool_accum);
+    m.impl("pool_finish", &pool_finish);
     m.impl("ar_all_reduce", &ar_all_reduce);
     m.impl("ar_all_reduce_norm", &ar_all_reduce_norm);
 }

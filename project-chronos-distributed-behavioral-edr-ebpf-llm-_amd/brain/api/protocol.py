@@ -87,6 +87,29 @@ token sampled at output index i (csrc/kernels/logprobs.hip computes them on the 
   (EngineConfig.max_logprobs);
 * a backend that cannot produce them (server started with ``--max-logprobs 0``, the fake backend) answers normally and
   names ``"logprobs"`` in ``ignored_options``.
+
+Embeddings (``POST /api/embed`` ``{"model", "input": str | [str], "truncate": true, "options": {"num_ctx"},
+"keep_alive"}`` -> ``{"model", "embeddings": [[...], ...], "total_duration", "load_duration", "prompt_eval_count"}``,
+and Ollama's legacy ``POST /api/embeddings`` ``{"model", "prompt"}`` -> ``{"embedding": [...]}``, the same vector):
+
+* an input is embedded as a raw prompt: BOS followed by its tokens, no chat template.  An empty string is its BOS-only
+  sequence (a deviation: Ollama answers an empty vector for it); ``"input": []`` gives ``"embeddings": []``;
+* the vector comes from the *final-RMSNorm hidden state* (the model's last layer output after the final norm, with the
+  checkpoint's own norm weight, the state the LM head would read), pooled over the prompt's tokens on the device
+  (csrc/kernels/pool.hip) and returned *L2-normalised, fp32* — by both endpoints (a deviation for the legacy one,
+  which Ollama does not normalise);
+* pooling is the server's choice (``--embed-pooling``, EngineConfig.embed_pooling): ``mean`` (default) is the direction
+  of the mean over all tokens — every token's state is needed, so such a request takes no prefix-cache hit;
+  ``last`` is the last token's state, which reuses cached prefix blocks like a generate request: the cheap mode for
+  event chains behind one long shared instruction prefix;
+* ``truncate`` (default true) keeps the first ``num_ctx`` (else max_model_len) tokens of an input that is too long;
+  ``truncate: false`` makes that a 400.  ``prompt_eval_count`` is the total over the inputs, after truncation;
+  durations are in ns; the order of ``embeddings`` is the order of ``input``;
+* 400: a missing ``input`` (``prompt``), one that is neither a string nor a list of strings, a ``truncate`` that is
+  not a boolean, a bad ``options.num_ctx``, invalid JSON.  An engine failure is a 500, ``--request-timeout`` a 504;
+* a backend that does not embed (tensor / context parallel groups, the data-parallel router, the fake backend)
+  answers 501 ``{"error": ...}``; a server started with ``--kv-dtype fp8`` answers 400 with the engine's error
+  (embeddings are served with a bf16 KV cache only: e4m3 K / V moves the vectors by 2 - 6 % of their largest component).
 """
 from __future__ import annotations
 
@@ -237,6 +260,49 @@ class GenerateParams:
                     raise BadRequest("each message needs a role and content")
             p.messages = msgs
         return p
+
+
+@dataclass
+class EmbedParams:
+    model: str = "llama3"
+    inputs: tuple = ()
+    truncate: bool = True
+    num_ctx: int = 0
+    legacy: bool = False  # /api/embeddings: one "prompt", one "embedding"
+
+    @classmethod
+    def parse(cls, body: dict, legacy: bool = False) -> "EmbedParams":
+        if not isinstance(body, dict):
+            raise BadRequest("request body must be a JSON object")
+        key = "prompt" if legacy else "input"
+        if key not in body:
+            raise BadRequest(f"missing {key}")
+        v = body[key]
+        if isinstance(v, str):
+            inputs = (v,)
+        elif not legacy and isinstance(v, list) and all(isinstance(x, str) for x in v):
+            inputs = tuple(v)
+        else:
+            raise BadRequest("prompt must be a string" if legacy else "input must be a string or a list of strings")
+        truncate = body.get("truncate", True)
+        if not isinstance(truncate, bool):
+            raise BadRequest("truncate must be true or false")
+        opts = body.get("options") or {}
+        if not isinstance(opts, dict):
+            raise BadRequest("options must be an object")
+        n = opts.get("num_ctx", 0) or 0
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise BadRequest("options.num_ctx must be a positive integer")
+        return cls(str(body.get("model") or "llama3"), inputs, truncate, n, legacy)
+
+
+def embed_response(model: str, reqs: list, t0: float, legacy: bool = False) -> dict:
+    """The /api/embed body (``legacy``: /api/embeddings') from the finished engine requests, in input order."""
+    vecs = [[float(x) for x in r.embedding.tolist()] for r in reqs]
+    if legacy:
+        return {"embedding": vecs[0]}
+    return {"model": model, "embeddings": vecs, "total_duration": _ns(time.perf_counter() - t0), "load_duration": 0,
+            "prompt_eval_count": sum(len(r.prompt_ids) for r in reqs)}
 
 
 def chat_prompt_ids(tok, messages: list) -> list:

@@ -4,6 +4,8 @@ Endpoints:
   POST /api/generate   the sensor contract (chronos_sensor.py:117-120): stream=false -> one JSON object whose
                        ``response`` is the (constrained) model text; stream=true -> NDJSON chunks (Ollama default)
   POST /api/chat       Llama-3 chat template over ``messages``
+  POST /api/embed      L2-normalised fp32 embeddings of ``input`` (a string or a list), pooled on the device from the
+                       final-RMSNorm hidden state (protocol.py);  POST /api/embeddings  the legacy one-``prompt`` form
   GET  /api/tags, POST /api/show, GET /api/ps, GET /api/version, GET /      model listing / health (Ollama shapes)
   GET  /healthz        liveness + engine state;   GET /metrics   Prometheus text (utils/metrics.py)
 
@@ -25,8 +27,8 @@ from aiohttp import web
 
 from ...utils import freeze_startup_objects
 from ...utils.metrics import METRICS
-from .protocol import (OLLAMA_VERSION, BadRequest, GenerateParams, StopFilter, apply_stop, chat_response,
-                       stop_context_ids,
+from .protocol import (OLLAMA_VERSION, BadRequest, EmbedParams, GenerateParams, StopFilter, apply_stop, chat_response,
+                       embed_response, stop_context_ids,
                        final_fields, generate_response, logprobs_field, now_iso, penalties_ignored)
 
 log = logging.getLogger("chronos.api")
@@ -142,6 +144,39 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
     async def chat(request):
         return await _run(await _params(request, chat=True), True, request)
 
+    async def _embed(request, legacy: bool):
+        def err(msg, status):
+            return web.json_response({"error": msg}, status=status)
+
+        try:
+            body = await request.json()
+        except Exception:
+            return err("invalid JSON body", 400)
+        try:
+            p = EmbedParams.parse(body, legacy=legacy)
+        except (BadRequest, ValueError, TypeError) as e:
+            return err(str(e), 400)
+        fn = getattr(backend, "embed", None)
+        if fn is None:
+            return err("this backend does not serve embeddings", 501)
+        t0 = time.perf_counter()
+        try:
+            coro = fn(list(p.inputs), p.truncate, p.num_ctx or None)
+            reqs = await (asyncio.wait_for(coro, request_timeout) if request_timeout else coro)
+        except asyncio.TimeoutError:
+            return err("embedding timed out", 504)
+        for r in reqs:
+            if getattr(r, "error", None):  # rejected by the engine: the client's fault; a failed step: ours
+                internal = (getattr(r, "meta", None) or {}).get("internal_error", False)
+                return err(r.error, 500 if internal else 400)
+        return web.json_response(embed_response(p.model or model_name, reqs, t0, legacy))
+
+    async def embed(request):
+        return await _embed(request, False)
+
+    async def embeddings(request):
+        return await _embed(request, True)
+
     def _model_entry():
         info = backend.info() if hasattr(backend, "info") else {}
         # (packed-only MXFP4 is the same numbers as "mxfp4": one quantization level)
@@ -183,7 +218,8 @@ def make_app(backend, model_name: str = "llama3", request_timeout: float | None 
         return web.Response(text=METRICS.render(), content_type="text/plain")
 
     app.add_routes([
-        web.post("/api/generate", generate), web.post("/api/chat", chat), web.get("/api/tags", tags),
+        web.post("/api/generate", generate), web.post("/api/chat", chat), web.post("/api/embed", embed),
+        web.post("/api/embeddings", embeddings), web.get("/api/tags", tags),
         web.get("/api/ps", ps), web.post("/api/show", show), web.get("/api/version", version), web.get("/", root),
         web.get("/healthz", healthz), web.get("/metrics", metrics),
     ])
@@ -272,6 +308,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--penalty-window", type=int, default=64,
                     help="history window of repeat / frequency / presence penalties, the most repeat_last_n can "
                          "reach (0-1024); 0 = penalties are not offered")
+    ap.add_argument("--embed-pooling", choices=["mean", "last"], default="mean",
+                    help="how /api/embed pools the final-norm hidden states: mean over all tokens (takes no prefix-cache "
+                         "hit) or the last token's (reuses cached prefix blocks)")
     ap.add_argument("--roctx", action="store_true", help="emit roctx ranges for rocprofv3 --marker-trace")
     return ap
 
@@ -294,7 +333,8 @@ def main(argv=None) -> int:
                            weight_dtype=a.weights,
                            **({} if a.fp8_a16_rows is None else {"fp8_a16_rows": a.fp8_a16_rows}),
                            request_timeout_s=a.request_timeout, tp_sequence_parallel=a.sequence_parallel,
-                           max_logprobs=a.max_logprobs, penalty_window=a.penalty_window)
+                           max_logprobs=a.max_logprobs, penalty_window=a.penalty_window,
+                           embed_pooling=a.embed_pooling)
         if a.tp > 1 or a.cp > 1:
             if a.tp > 1 and a.cp > 1:
                 raise SystemExit("--tp and --cp are exclusive (CP ranks hold full weights)")

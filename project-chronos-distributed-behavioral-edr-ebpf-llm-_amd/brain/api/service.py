@@ -130,6 +130,13 @@ class EngineService:
                 frequency_penalty=params.frequency_penalty, presence_penalty=params.presence_penalty,
                 repeat_last_n=params.repeat_last_n, min_p=params.min_p, typical_p=params.typical_p,
                 mirostat=params.mirostat, mirostat_tau=params.mirostat_tau, mirostat_eta=params.mirostat_eta)
+        elif kind == "embed":
+            _, text, truncate, num_ctx, on_done, handle = item
+            if handle.get("cancelled"):
+                self.engine.stats["cancelled"] += 1
+                return
+            handle["req"] = self.engine.submit_embed(text, max_len=num_ctx or None, truncate=truncate,
+                                                     callback=on_done)
         elif kind == "cancel":
             req = item[1].get("req")
             if req is not None and not req.done_reason:
@@ -167,6 +174,28 @@ class EngineService:
             return await fut
         except asyncio.CancelledError:  # caller timed out / disconnected: free the engine slot
             self._cancel(handle)
+            raise
+
+    async def embed(self, inputs, truncate: bool = True, num_ctx: int | None = None) -> list:
+        """One embedding request per input through the scheduler queue (tokenised by the engine at admission); returns
+        the finished requests in input order.  A caller that gives up cancels whatever is still in flight."""
+        loop = asyncio.get_running_loop()
+        futs, handles = [], []
+        for text in inputs:
+            fut: asyncio.Future = loop.create_future()
+            handle: dict = {}
+
+            def done(req: Request, fut=fut):
+                loop.call_soon_threadsafe(lambda: fut.done() or fut.set_result(req))
+
+            futs.append(fut)
+            handles.append(handle)
+            self._q.put(("embed", text, bool(truncate), num_ctx, done, handle))
+        try:
+            return list(await asyncio.gather(*futs))
+        except asyncio.CancelledError:
+            for h in handles:
+                self._cancel(h)
             raise
 
     async def generate_stream(self, params: GenerateParams) -> AsyncIterator[tuple[str, Optional[Request]]]:
@@ -250,6 +279,8 @@ class LockstepService(EngineService):
         self.broken = False
         self.on_fatal = on_fatal
         super().__init__(tpe.engine, model_name, step_deadline_s)
+
+    embed = None  # embeddings are served at TP = 1 only: the server answers 501 for a backend without ``embed``
 
     def _error_req(self, ids, reason: str) -> Request:
         r = Request(-1, list(ids), None, 0)

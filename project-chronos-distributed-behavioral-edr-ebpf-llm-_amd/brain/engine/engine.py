@@ -26,6 +26,12 @@ Replaces what Ollama + llama.cpp did for the reference (SURVEY.md §1.2 N4, §3.
   chunk i+1 while the GPU computes chunk i; after an idle period the chunks ramp up from ``prefill_ramp`` tokens so
   the GPU is not left waiting for the first chunk's tokenization.
 
+* **embeddings** (``submit_embed``): a request kind that ends after its prompt.  Its chunks ride in the prefill and mixed
+  steps with everyone else, the forward's pool hook (csrc/kernels/pool.hip) sums the final-RMSNorm hidden states of
+  its rows into the slot's fp32 accumulator, and when the prompt ends it leaves before the sampler: the vector is
+  finished on the device and copied to pinned memory behind an event, its slot and blocks go back at once, and it
+  completes at a later step without a stream synchronise.
+
 The reference's ``analyze_sequence`` blocked the sensor for one chain at a time (quirk Q1); here thousands of chains
 are in flight and each returns as soon as its own verdict closes.
 """
@@ -172,6 +178,11 @@ class EngineConfig:
     # a request's repeat_last_n above W is clamped to W.  Jump-forward stays on: forced runs enter the history through
     # the output ring.
     penalty_window: int = 0
+    # Embedding requests (Engine.submit_embed, csrc/kernels/pool.hip): how the final-RMSNorm hidden states of a prompt
+    # become its vector.  "mean": the direction of their sum over every token — such a request takes no prefix-cache
+    # hit, because every token's hidden state has to be computed; "last": the last token's, which reuses cached prefix
+    # blocks like any request (the cheap mode for chains behind one long shared instruction prefix)
+    embed_pooling: str = "mean"
 
 
 @dataclass
@@ -201,6 +212,10 @@ class Request:
     mirostat_tau: float = 5.0
     mirostat_eta: float = 0.1
     mirostat_mu: float = 10.0
+    # embedding request (Engine.submit_embed): the pooling mode, "mean" or "last" (None = a generating request), and,
+    # once done_reason is "embed", the L2-normalised vector (CPU fp32 [hidden])
+    embed: Optional[str] = None
+    embedding: Optional[torch.Tensor] = None
     # runtime
     pending_text: Optional[tuple] = None  # (prompt, system, raw) until tokenized at admission
     slot: int = -1
@@ -367,6 +382,13 @@ class Engine:
         # asked); _snap_mu: the harvest snapshots' pinned copies of mu
         self.s_mion = self.s_mimu = self.s_mitau = self.s_mieta = self.s_mim = self.s_milnz = self.s_mimark = None
         self._snap_mu: Optional[list] = None
+        # embedding requests: per-slot fp32 accumulators [max_slots, hidden], allocated (zeroed) when the first one is
+        # admitted (None = never asked); _embed_pending: (event, pinned vectors, requests) of finished prompts whose
+        # vectors are on their way to the host
+        if cfg.embed_pooling not in ("mean", "last"):
+            raise ValueError(f"embed_pooling must be mean or last, not {cfg.embed_pooling!r}")
+        self.s_pool: Optional[torch.Tensor] = None
+        self._embed_pending: collections.deque = collections.deque()
         self.ar = torch.arange(S + 1, **i32)
         self.ar64 = torch.arange(S, dtype=torch.int64, device=dev)
         # ---- scheduling state ----
@@ -471,11 +493,61 @@ class Engine:
             self.waiting.append(req)
         return req
 
+    def submit_embed(self, prompt: str | list, pooling: str | None = None, max_len: int | None = None,
+                     truncate: bool = True, callback: Callable[[Request], None] | None = None,
+                     meta: dict | None = None) -> Request:
+        """Queue an embedding request: the normal chunked prefill of ``prompt`` (token ids, or text that is tokenised
+        lazily at admission as a raw prompt: BOS + its tokens, no chat template), no decode.  It finishes with
+        ``done_reason == "embed"`` and ``Request.embedding``, the L2-normalised fp32 vector pooled from the final-RMSNorm
+        hidden states (``pooling`` "mean" or "last", default ``EngineConfig.embed_pooling``).  A prompt longer than the
+        window (``max_len``, within ``max_model_len``) keeps its first tokens when ``truncate``, else it is an error.
+        Engines with TP / CP ranks or an fp8 KV cache finish the request with an error instead."""
+        mode = pooling or self.cfg.embed_pooling
+        if mode not in ("mean", "last"):
+            raise ValueError(f"pooling must be mean or last, not {mode!r}")
+        req = Request(next(self._rid), list(prompt) if isinstance(prompt, list) else [], None, 0, 0.0, 0, callback,
+                      meta or {})
+        req.embed = mode
+        req.meta["truncate"] = bool(truncate)
+        if max_len:
+            req.meta["max_len"] = min(int(max_len), self.cfg.max_model_len)
+        req.t_submit = time.perf_counter()
+        if self.tp.world > 1 or self.cp.world > 1:
+            req.error = "embeddings are served at TP = 1 only"
+        elif self.model.cfg.hidden_size not in ops.POOL_HIDDEN:
+            req.error = f"embeddings need a hidden size in {ops.POOL_HIDDEN}, not {self.model.cfg.hidden_size}"
+        elif self.model.w.final_norm is None:
+            req.error = "the model's weights carry no final_norm"
+        elif self.cfg.kv_dtype != "bf16":
+            # measured on the GPU: with e4m3 K / V (three mantissa bits) the vectors are 2.0 - 6.2 % of their largest
+            # component off the bf16 ones, outside the project's 2 % whole-model rule (profiles/embed/)
+            req.error = f"embeddings are served with a bf16 KV cache only, not kv_dtype={self.cfg.kv_dtype!r}"
+        if req.error:
+            self._finish(req, "error")
+            return req
+        if not isinstance(prompt, list):
+            req.pending_text = (prompt, None, True)
+        elif not self._check_length(req):
+            return req
+        with self._lock:
+            self.waiting.append(req)
+        return req
+
     def _check_length(self, req: Request) -> bool:
         """Clamp num_predict to the context left after the prompt; finish the request with an error if nothing (or
-        less than the format's shortest output) fits."""
+        less than the format's shortest output) fits.  An embedding request generates nothing: its prompt may fill
+        the window, and is cut to it when the request truncates."""
         ids = req.prompt_ids
         limit = req.meta.get("max_len", self.cfg.max_model_len)
+        if req.embed:
+            if len(ids) > limit and req.meta.get("truncate", True):
+                ids = req.prompt_ids = ids[:limit]
+            if len(ids) > limit or not ids:
+                what = "num_ctx" if limit < self.cfg.max_model_len else "max_model_len"
+                req.error = f"prompt of {len(ids)} tokens exceeds {what} {limit}" if ids else "empty prompt"
+                self._finish(req, "error")
+                return False
+            return True
         req.num_predict = n = min(req.num_predict, limit - len(ids))
         if n <= 0:
             what = "num_ctx" if limit < self.cfg.max_model_len else "max_model_len"
@@ -489,7 +561,7 @@ class Engine:
         return True
 
     def has_work(self) -> bool:
-        return bool(self.waiting or self.prefilling or self.running or self._deferred)
+        return bool(self.waiting or self.prefilling or self.running or self._deferred or self._embed_pending)
 
     def step(self) -> list[Request]:
         """One scheduling iteration: admit + prefill if anything is waiting, else one decode burst.
@@ -500,6 +572,8 @@ class Engine:
         pc, ph = time.perf_counter, self.phase_s
         t0 = pc()
         reaped = self._reap()
+        if self._embed_pending:
+            reaped += self._embed_poll(wait=not (self.waiting or self.prefilling or self.running))
         with trace.range("admit"):
             self._admit()
         t1 = pc()
@@ -557,12 +631,16 @@ class Engine:
             todo, self._cancels = self._cancels, []
         if self.cfg.request_timeout_s > 0:
             dl = time.perf_counter() - self.cfg.request_timeout_s
-            todo += [(r, "timeout") for r in (*self.waiting, *self.prefilling, *self.running.values())
+            todo += [(r, "timeout") for r in (*self.waiting, *self.prefilling, *self.running.values(),
+                                              *(r for _, _, rs in self._embed_pending for r in rs))
                      if r.t_submit < dl]
         out, reset = [], []
         for req, reason in todo:
             if req.done_reason:
                 continue  # already finished (or reaped twice)
+            if req.embed and any(req in rs for _, _, rs in self._embed_pending):
+                req.meta["cancel_reason"] = reason  # its vector is on its way: dropped when it arrives (_embed_poll)
+                continue
             if req in self.prefilling:
                 # Its prompt blocks are published in the prefix cache and may already be shared by a later request
                 # that relies on this prefill computing them: finish the prefill, then drop it (_prefill_step).
@@ -602,8 +680,10 @@ class Engine:
         than patched; the device slot state is reset best-effort (the device itself may be gone)."""
         self._flush_deferred()  # verdicts harvested before the fault are complete: finish them normally
         with self._lock:
-            reqs = [*self.waiting, *self.prefilling, *self.running.values()]
+            reqs = [*self.waiting, *self.prefilling, *self.running.values(),
+                    *(r for _, _, rs in self._embed_pending for r in rs)]
             self.waiting.clear()
+            self._embed_pending.clear()
             self._cancels = []
         self.prefilling = []
         self._copies = []
@@ -622,6 +702,8 @@ class Engine:
             self.s_bt.zero_()
             self.s_pos.zero_()
             self.s_ctx.fill_(1)
+            if self.s_pool is not None:
+                self.s_pool.zero_()
         except Exception:  # noqa: BLE001 — a dead device must not stop the error replies below
             log.exception("slot state reset after a failed step")
         out = []
@@ -682,12 +764,16 @@ class Engine:
                                  f"{self.blocks.num_blocks - 1}")
                     self._finish(req, "error")
                     continue
-                shared = self.blocks.lookup(req.prompt_ids)  # cached prefix blocks (already referenced)
+                # (mean pooling needs every token's hidden state: such a request takes no prefix hit, full or partial)
+                nohit = req.embed == "mean"
+                shared = [] if nohit else self.blocks.lookup(req.prompt_ids)  # cached prefix blocks (already referenced)
                 if not self.blocks.can_alloc(nblk - len(shared) + (wm if self.running else 0)):
                     self.blocks.release(shared)
                     break
                 self.waiting.popleft()
-                part = self.blocks.lookup_partial(req.prompt_ids, len(shared)) if self.cfg.partial_prefix else None
+                part = None
+                if self.cfg.partial_prefix and not nohit:
+                    part = self.blocks.lookup_partial(req.prompt_ids, len(shared))
                 if part is not None and not self.blocks.can_alloc(nblk - len(shared)):
                     self.blocks.release([part[0]])  # its reference took an evictable block out of the free pool
                     part = None
@@ -706,6 +792,9 @@ class Engine:
                 # every layer writes the step's K/V (rope_kv_write) before any of its attention reads it.
                 self.blocks.register(req.prompt_ids, req.blocks)
                 req.slot = self.free_slots.pop()
+                if req.embed and self.s_pool is None:
+                    self.s_pool = torch.zeros(self.cfg.max_slots, self.model.cfg.hidden_size, dtype=torch.float32,
+                                              device=self.device)
                 req.t_admit = time.perf_counter()
                 self.prefilling.append(req)
                 budget -= len(req.prompt_ids) - req.prefilled
@@ -906,9 +995,95 @@ class Engine:
                 self.blocks.register(req.prompt_ids, req.blocks)
         self.stats["prefill_tokens"] += sum(len(c) for c in chunks)
         self.stats["prefill_steps"] += 1
+        emb = [r for r in done_reqs if r.embed] if self.s_pool is not None else None
+        if emb:  # they never decode: no slot state, no sampler row, no _start_running
+            keep = [(i, r) for i, r in zip(done_rows, done_reqs) if not r.embed]
+            done_rows, done_reqs = [i for i, _ in keep], [r for _, r in keep]
+            self._embed_done(emb)
         if done_reqs:
             self._init_slots(done_reqs)
         return done_rows, done_reqs
+
+    # ---- embedding requests -----------------------------------------------------------------------------------------
+    def _pool_attach(self, sb: StepBatch, chunks, reqs) -> None:
+        """The pool hook of a prefill / mixed forward that carries embedding requests: per sequence of the step the
+        row range that ops.pool_accum adds to the request's slot accumulator — the whole chunk under mean pooling, the
+        finishing chunk's last row under last-token pooling, nothing (sel -1) for everyone else.  A step whose
+        sequences all embed (and that has no decode rows) skips the LM head."""
+        if self.s_pool is None or not any(r.embed for r in reqs):  # (an engine never asked: one test per forward)
+            return
+        q, sel, at = [], [], 0
+        for r, ch in zip(reqs, chunks):
+            lo, at = at, at + len(ch)
+            if r.embed == "mean":
+                q.append((lo, at))
+                sel.append(r.slot)
+            elif r.embed == "last" and r.prefilled + len(ch) == len(r.prompt_ids):
+                q.append((at - 1, at))
+                sel.append(r.slot)
+            else:
+                q.append((lo, lo))
+                sel.append(-1)
+        sb.pool = (h2d(torch.tensor(q, dtype=torch.int32).view(-1, 2), self.device),
+                   h2d(torch.tensor(sel, dtype=torch.int32), self.device), self.s_pool)
+        sb.want_logits = sb.dec is not None or not all(r.embed for r in reqs)
+
+    def _embed_done(self, emb) -> None:
+        """Embedding requests whose last chunk's forward was just queued: queue ops.pool_finish for their accumulator
+        rows (which also zeroes them for the slots' next owners) and the copy of the vectors to pinned host memory, then
+        give back their blocks and slots — later launches are stream-ordered behind these.  The requests complete at a
+        later step(), once the copy's event has (``_embed_poll``); the stream is never synchronised."""
+        H = self.model.cfg.hidden_size
+        out = torch.empty(len(emb), H, dtype=torch.float32, device=self.device)
+        ops.pool_finish(self.s_pool, h2d(torch.tensor([r.slot for r in emb], dtype=torch.int32), self.device),
+                        self.model.w.final_norm, out)
+        ev = None
+        if self.device.type == "cuda":
+            host = torch.empty(len(emb), H, dtype=torch.float32, pin_memory=True)
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            host = out
+        now = time.perf_counter()
+        for r in emb:
+            r.t_first = now
+            self.prefilling.remove(r)
+            self.blocks.release(r.blocks)
+            r.blocks = []
+            # (the slot's device state was never published: its block-table row still points at the scratch block)
+            self.free_slots.append(r.slot)
+            r.slot = -1
+        self.free_slots.sort(reverse=True)
+        self._embed_pending.append((ev, host, emb))
+
+    def _embed_poll(self, wait: bool = False) -> list[Request]:
+        """Complete the embedding requests whose vectors have arrived, oldest first.  ``wait``: nothing else is left to
+        schedule, so wait for the oldest copy's event (the event, not the stream) instead of spinning."""
+        out = []
+        while self._embed_pending:
+            ev, host, reqs = self._embed_pending[0]
+            if ev is not None and not ev.query():
+                if not wait:
+                    break
+                ev.synchronize()
+            wait = False
+            self._embed_pending.popleft()
+            for i, r in enumerate(reqs):
+                if r.done_reason:
+                    continue
+                reason = r.meta.pop("cancel_reason", None)
+                if reason:  # cancelled or timed out on the way: the vector is dropped
+                    r.error = f"request {reason}"
+                    self.stats[reason] += 1
+                    self._finish(r, reason)
+                else:
+                    r.embedding = host[i].clone()
+                    self.stats["embed_requests"] += 1
+                    self.stats["embed_tokens"] += len(r.prompt_ids)
+                    self._finish(r, "embed")
+                out.append(r)
+        return out
 
     def _init_slots(self, done_reqs) -> None:
         """A finished prompt's slot state, ready for its first sampled token.  Its block-table row is published only
@@ -1127,6 +1302,7 @@ class Engine:
             split = 2 if (self.tp.world > 1 and self.cfg.tp_overlap and ntok >= self.cfg.tp_overlap_min_tokens) else 1
             sb = make_prefill_batch(chunks, starts, bts, self.model.cfg, self.tp, self.device,
                                     max_blocks=self.max_blocks_per_seq, nqt=self.cfg.prefill_nqt, split=split)
+            self._pool_attach(sb, chunks, reqs)
             logits = self.model.forward(sb, self.kv)
         done_rows, done_reqs = self._prefill_done(reqs, chunks)
         if not done_reqs:
@@ -1174,6 +1350,7 @@ class Engine:
         sb.dec = StepBatch(self.s_ids[:n], self.s_pos[:n], self.ar[:n], self.s_bt[:n], self.ar[:n + 1], self.s_ctx[:n],
                            self.ar64[:n], None, n, 1, self._nsplit(n, self._ctx_class()), casc=self._casc)
         sb.last_idx = torch.cat([sb.last_idx, tp_ + self.ar64[:n]])
+        self._pool_attach(sb, chunks, reqs)
         logits = self.model.forward(sb, self.kv)
         done_rows, done_reqs = self._prefill_done(reqs, chunks)
         # logits rows: the prefill sequences' last tokens, then decode row i at bp + i

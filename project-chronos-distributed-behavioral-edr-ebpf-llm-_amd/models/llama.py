@@ -257,6 +257,9 @@ class LlamaWeights:
     norms_folded: bool = False
     # packed-only MXFP4 (Q4Tensor.w is None) on a GPU: the one bf16 expansion buffer all projections share
     scratch: Optional["ops.W4Scratch"] = None
+    # the raw final RMSNorm weight [d], kept whether or not ``norm`` was folded into the LM head (and replicated on every
+    # TP rank, like ``norm``): an embedding is pooled from the final-norm hidden state, which a folded head hides
+    final_norm: Optional[torch.Tensor] = None
 
     def attach_scratch(self) -> None:
         """Packed-only MXFP4 on a GPU: allocate the expansion scratch (the largest projection's N K bf16 elements, at a
@@ -273,6 +276,8 @@ class LlamaWeights:
 
     def nbytes(self) -> int:
         n = 2 * (self.embed.numel() + self.norm.numel() + (0 if self.lm_head is self.embed else self.lm_head.numel()))
+        if self.final_norm is not None and self.final_norm is not self.norm:
+            n += 2 * self.final_norm.numel()
         for l in self.layers:
             for t in (l.attn_norm, l.wqkv, l.wo, l.mlp_norm, l.w_gu, l.w_down):
                 n += t.nbytes() if isinstance(t, (QTensor, Q4Tensor)) else 2 * t.numel()
@@ -397,7 +402,8 @@ def random_weights(cfg: LlamaConfig, tp: TPContext | None = None, device="cpu", 
         lm_full = rnd(cfg.vocab_size, d)
         lm_head = lm_full[tp.rank * vs:(tp.rank + 1) * vs].contiguous()
         del lm_full
-    return LlamaWeights(embed, layers, ones(d), lm_head, vocab_start=tp.rank * vs, norms_folded=fold_norms)
+    return LlamaWeights(embed, layers, ones(d), lm_head, vocab_start=tp.rank * vs, norms_folded=fold_norms,
+                        final_norm=ones(d))
 
 
 # ---- checkpoint loaders ----------------------------------------------------------------------------------------
@@ -457,8 +463,10 @@ def load_hf(path: str, tp: TPContext | None = None, device="cpu", dtype=torch.bf
         lm_head = embed
     else:
         lm_head = get("lm_head.weight")[tp.rank * vs:(tp.rank + 1) * vs].to(device=device, dtype=dtype).contiguous()
+    raw_norm = norm
     norm, lm_head = _final(norm, lm_head, fold_norms)
-    return cfg, LlamaWeights(embed, layers, norm, lm_head, vocab_start=tp.rank * vs, norms_folded=fold_norms)
+    return cfg, LlamaWeights(embed, layers, norm, lm_head, vocab_start=tp.rank * vs, norms_folded=fold_norms,
+                             final_norm=raw_norm)
 
 
 def load_meta(path: str, tp: TPContext | None = None, device="cpu", dtype=torch.bfloat16,
@@ -493,8 +501,10 @@ def load_meta(path: str, tp: TPContext | None = None, device="cpu", dtype=torch.
         layers.append(assemble_layer(cfg, tp, full, device, dtype, weight_dtype, fold_norms))
     norm = cat("norm.weight", 0).to(device=device, dtype=dtype)
     lm_head = cat("output.weight", 0)[tp.rank * vs:(tp.rank + 1) * vs].to(device=device, dtype=dtype).contiguous()
+    raw_norm = norm
     norm, lm_head = _final(norm, lm_head, fold_norms)
-    return cfg, LlamaWeights(embed, layers, norm, lm_head, vocab_start=tp.rank * vs, norms_folded=fold_norms)
+    return cfg, LlamaWeights(embed, layers, norm, lm_head, vocab_start=tp.rank * vs, norms_folded=fold_norms,
+                             final_norm=raw_norm)
 
 
 def load_checkpoint(path: str, tp: TPContext | None = None, device="cpu", weight_dtype: str = "bf16",
@@ -566,6 +576,13 @@ class StepBatch:
     # the split-K decode kernel with all of a sequence's tokens in one pass over its K/V (ops.paged_attention
     # max_q) instead of the prefill tiles, whose per-tile workgroups each stream the whole context
     rows_dec: Optional[tuple] = None
+    # embedding requests (ops.pool_accum after the last layer, over this batch's prefill rows): (q_rows [B, 2] int32 row
+    # ranges, sel [B] int32 accumulator rows or -1, acc [S, H] fp32), device tensors owned by the engine.  None: the
+    # forward launches what it always did
+    pool: Optional[tuple] = None
+    # False: no sequence of this step generates (every one is an embedding request): the final norm and the LM head are
+    # skipped and the forward returns None
+    want_logits: bool = True
 
 
 # decode-form attention for tiny chunks over long contexts (StepBatch.rows_dec): at least this much context (the
@@ -631,7 +648,7 @@ def to_device(sb: StepBatch, device) -> StepBatch:
     mv = lambda t: h2d(t, device)  # noqa: E731
     return StepBatch(mv(sb.ids), mv(sb.pos), mv(sb.tok_seq), mv(sb.block_table), mv(sb.q_start), mv(sb.ctx_len),
                      mv(sb.last_idx), mv(sb.tiles), sb.ntiles, sb.nqt, sb.nsplit, sb.parts, sb.cp, sb.dec, sb.casc,
-                     sb.rows_dec)
+                     sb.rows_dec, sb.pool, sb.want_logits)
 
 
 # -----------------------------------------------------------------------------------------------------------------
@@ -878,6 +895,24 @@ class LlamaModel:
         logits = tp.all_gather_last(logits)
         return logits if logits.dtype == logits_dtype else logits.to(logits_dtype)
 
+    def _pool(self, dn, st: dict):
+        """The embedding hook after the last layer: ops.pool_accum over the summed residual stream of the step's
+        prefill rows (with ``sb.dec``, the first ``sb.ids.numel()`` rows).  A producer's ResidOut carries the sum; the
+        caller goes on to its usual final norm of the sampled rows.  A plain down projection is first added to the residual for all rows
+        (add_rmsnorm, in place, which also yields every row's final norm): the sampled rows of that are returned, None
+        when the caller still has to take the final norm of the sampled rows itself."""
+        sb = st["sb"]
+        if self.tp.world > 1 or sb.cp is not None:
+            raise RuntimeError("embeddings are served at TP = 1 only")
+        q_rows, sel, acc = sb.pool
+        tp_rows = sb.ids.numel()
+        if isinstance(dn, ops.ResidOut):
+            ops.pool_accum(dn.s[:tp_rows], self.cfg.rms_eps, q_rows, sel, acc)
+            return None
+        y = ops.add_rmsnorm(dn, st["resid"], self.w.norm, self.cfg.rms_eps)
+        ops.pool_accum(st["resid"][:tp_rows], self.cfg.rms_eps, q_rows, sel, acc)
+        return y.index_select(0, sb.last_idx) if sb.want_logits else None
+
     def forward(self, sb: StepBatch, kv: KVCache, logits_dtype=torch.bfloat16) -> torch.Tensor:
         """Returns logits [B, V] for the token at sb.last_idx of every sequence (full vocab on every TP rank).
 
@@ -930,7 +965,13 @@ class LlamaModel:
                     work.wait()
                 if li + 1 < L:
                     st["x"] = self._norm(dn, st, w.layers[li + 1].attn_norm, reduce=fuse)
-                elif isinstance(dn, ops.ResidOut) and st["sb"].tiles is None:  # decode: every token is sampled
+                    continue
+                if st["sb"].pool is not None:
+                    x = self._pool(dn, st)
+                    if x is not None or not st["sb"].want_logits:
+                        st["x"] = x
+                        continue
+                if isinstance(dn, ops.ResidOut) and st["sb"].tiles is None:  # decode: every token is sampled
                     st["x"] = self._norm(dn, st, w.norm)
                 elif fuse and st["sb"].tiles is None:  # TP decode: every token is sampled
                     st["x"] = self._norm(dn, st, w.norm, reduce=True)
@@ -944,6 +985,8 @@ class LlamaModel:
                     li_ = st["sb"].last_idx
                     st["x"] = ops.add_rmsnorm(dn.index_select(0, li_), st["resid"].index_select(0, li_), w.norm,
                                               cfg.rms_eps)
+        if not sb.want_logits:
+            return None
         x = states[0]["x"] if len(states) == 1 else torch.cat([ops.LazyNorm.force(st["x"]) for st in states])
         logits = ops.linear(x, w.lm_head)
         logits = tp.all_gather_last(logits)

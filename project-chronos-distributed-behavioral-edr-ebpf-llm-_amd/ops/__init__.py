@@ -5,7 +5,7 @@ extension (``_C*.so``, built by :mod:`chronos.native`) cannot be built or loaded
 the gloo-backed distributed tests, the CPU plumbing config) take :mod:`.reference`.
 
 Kernel sources: csrc/kernels/{elementwise,attention,sampler,logprobs,penalties,truncate,mirostat,
-w4_expand}.hip.
+w4_expand,pool}.hip.
 """
 from __future__ import annotations
 
@@ -490,6 +490,47 @@ def mirostat_row(x, legal, temperature: float, mu: float, dtype=torch.float32):
     """The reference survivors of one row (:func:`.reference.mirostat_row`): ``(keep, m, ln Z')`` or ``None`` for a
     forced step."""
     return ref.mirostat_row(x, legal, temperature, mu, dtype)
+
+
+POOL_HIDDEN = ref.POOL_HIDDEN
+
+
+def pool_accum(s: torch.Tensor, eps: float, q_rows: torch.Tensor, sel: torch.Tensor, acc: torch.Tensor) -> None:
+    """Embedding pooling over the un-normalised residual stream ``s`` [T, H] bf16 after the last layer:
+    ``acc[sel[b]] += sum over rows r in [q_rows[b, 0], q_rows[b, 1]) of s[r] * rsqrt(mean(s[r]^2) + eps)`` in fp32 (unit
+    norm weight: :func:`pool_finish` applies the real one to the sum).  ``q_rows`` [B, 2] and ``sel`` [B] are int32,
+    ``acc`` is [S, H] fp32; ``sel[b] = -1`` skips sequence b, ranges may be empty, rows outside every range are never
+    read, and two sequences must not select the same accumulator row.  Deterministic: the same call gives the same
+    bits on every launch (csrc/kernels/pool.hip)."""
+    if s.dim() != 2 or s.shape[1] not in POOL_HIDDEN or acc.dim() != 2 or acc.shape[1] != s.shape[1]:
+        raise ValueError(f"pool_accum: s [T, H] and acc [S, H] with H in {POOL_HIDDEN}, not {tuple(s.shape)} and "
+                         f"{tuple(acc.shape)}")
+    if _checking(s):
+        q, sl = q_rows.cpu().long(), sel.cpu().long()
+        _need(bool(((q[:, 0] >= 0) & (q[:, 1] <= s.shape[0])).all()), "pool_accum: row range outside s")
+        _need(bool(((sl >= -1) & (sl < acc.shape[0])).all()), "pool_accum: accumulator row out of range")
+        live = sl[sl >= 0]
+        _need(live.unique().numel() == live.numel(), "pool_accum: two sequences select one accumulator row")
+    if s.is_cuda:
+        _k().pool_accum(s, eps, q_rows, sel, acc)
+    else:
+        ref.pool_accum(s, eps, q_rows, sel, acc)
+
+
+def pool_finish(acc: torch.Tensor, rows: torch.Tensor, g: torch.Tensor, out: torch.Tensor) -> None:
+    """``out[i] = v / ||v||_2`` with ``v = g * acc[rows[i]]`` (zeros when the norm is 0), then ``acc[rows[i]] <- 0``.
+    ``g`` is the raw final norm weight [H] bf16, ``rows`` int32 [n], ``out`` fp32 [n, H]."""
+    if acc.dim() != 2 or acc.shape[1] not in POOL_HIDDEN or g.numel() != acc.shape[1]:
+        raise ValueError(f"pool_finish: acc [S, H] and g [H] with H in {POOL_HIDDEN}, not {tuple(acc.shape)} and "
+                         f"{tuple(g.shape)}")
+    if _checking(acc):
+        r = rows.cpu().long()
+        _need(bool(((r >= 0) & (r < acc.shape[0])).all()), "pool_finish: accumulator row out of range")
+        _need(r.unique().numel() == r.numel(), "pool_finish: a row is listed twice")
+    if acc.is_cuda:
+        _k().pool_finish(acc, rows, g, out)
+    else:
+        ref.pool_finish(acc, rows, g, out)
 
 
 def attention_tiles(q_lens: list[int], hq: int, hkv: int, nqt: int) -> list[tuple[int, int]]:

@@ -518,3 +518,36 @@ def mirostat_update(logits, row_of_slot, nout, out_tokens, temperature, mi_on, m
         if not bool(torch.isfinite(sobs)):
             continue
         mi_mu[slot] = mi_mu[slot] - mi_eta[slot] * (sobs - mi_tau[slot])
+
+
+POOL_HIDDEN = (256, 1024, 4096, 8192)  # the hidden sizes csrc/kernels/pool.hip is compiled for
+
+
+def pool_accum(s: torch.Tensor, eps: float, q_rows: torch.Tensor, sel: torch.Tensor, acc: torch.Tensor) -> None:
+    """acc[sel[b]] += sum over rows r in [q_rows[b, 0], q_rows[b, 1]) of s[r] * rsqrt(mean(s[r]^2) + eps), accumulated in
+    fp64 and added to the fp32 accumulator once per sequence (csrc/kernels/pool.hip).  ``sel[b] < 0`` (or past the
+    accumulator) skips the sequence, a range is clipped to the rows of ``s``, rows outside every range are never read."""
+    T, S = s.shape[0], acc.shape[0]
+    for b, row in enumerate(sel.tolist()):
+        if not 0 <= row < S:
+            continue
+        lo, hi = max(int(q_rows[b, 0]), 0), min(int(q_rows[b, 1]), T)
+        if hi <= lo:
+            continue
+        x = s[lo:hi].double()
+        inv = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps)
+        acc[row] = (acc[row].double() + (x * inv).sum(0)).to(acc.dtype)
+
+
+def pool_finish(acc: torch.Tensor, rows: torch.Tensor, g: torch.Tensor, out: torch.Tensor) -> None:
+    """out[i] = v / ||v||_2 with v = g * acc[rows[i]] (fp64; zeros when the norm is 0), then acc[rows[i]] <- 0.  A row
+    outside the accumulator gives zeros."""
+    S = acc.shape[0]
+    for i, row in enumerate(rows.tolist()):
+        if not 0 <= row < S:
+            out[i] = 0
+            continue
+        v = acc[row].double() * g.double()
+        n = v.pow(2).sum().sqrt()
+        out[i] = (v / n).to(out.dtype) if n > 0 else 0
+        acc[row] = 0
